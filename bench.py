@@ -22,12 +22,6 @@ import os
 import sys
 import time
 
-# Hardware queues per stream priority (ROCclr reads it when libamdhip64 loads, i.e. before `import torch`): a handle has one
-# compute stream and three side streams, the trackers one each; with the default of 4 a second handle's streams share
-# hardware queues with the first one's and wait behind its event barriers (two streams per GPU: 309 -> 318 FPS,
-# profiles/r06_hw_queues_and_cosine_priority_ab.txt).  An explicit setting in the environment wins.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -77,7 +71,12 @@ def main():
                   help="no GPU work: start the N ranks exactly as a real run does (self-launch, rendezvous, the "
                        "barrier / all-gather / max-over-ranks reduction of the timed region) over gloo and print the "
                        "contract line's launch fields -- what the CPU suite runs")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / "
+                       "float64, at most 64 MB in all: two builds run with the same arguments can be compared output for output")
   args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error("--steps must be at least 1 and --warmup at least 0")
 
   if "WORLD_SIZE" not in os.environ and args.gpus > 1:
     # `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU, the same launcher
@@ -169,15 +168,16 @@ def main():
     nn_match = (gal.astype(np.float32), seg, det.astype(np.float32))
     _ops.nn_cosine(*nn_match, device=local_rank)
   nn_calls = [0]
+  nn_cost = [None] * S          # per stream: the cost matrix of its last nn_matching call
 
   def step():
     r = step_no[0] % NROT
     step_no[0] += 1
-    for e, ds in zip(engs, dev_rot):
+    for i, (e, ds) in enumerate(zip(engs, dev_rot)):
       e.forward_device_async(ds[r].data_ptr(), ODT_DTYPE_U8)
       if nn_match is not None:
         for _ in range(B):
-          _ops.nn_cosine(*nn_match, device=local_rank)
+          nn_cost[i] = _ops.nn_cosine(*nn_match, device=local_rank)
           nn_calls[0] += 1
 
   def sync_all():
@@ -203,6 +203,7 @@ def main():
   dt = time.perf_counter() - t0
   dt, ranks_seen, rank_dts = reduce_timing(dt, rank, world, "cuda" if args.dist_backend == "nccl" else "cpu")
   rank_fps = [S * B * args.steps / t for t in rank_dts]
+  dumped = dump_outputs(args.dump_outputs, engs, nn_cost) if args.dump_outputs and rank == 0 else None
 
   # the timed region, checked: the outputs the LAST replayed forward of every stream left in HBM must equal, bit for
   # bit, a blocking odt_forward of the same frames through the host boundary -- and must be a non-trivial detection set
@@ -399,6 +400,8 @@ def main():
         "roofline": roofline,
     }
     out["extra"] = extra
+    if dumped is not None:
+      out["dump_outputs"] = dumped
     if world == 1 and not args.no_cpu_baseline:
       out["cpu_baseline"] = cpu_baseline(cfg, weights, frames, args.cpu_frames, multi)
     if world == 1 and S == 1 and not args.no_extras and not args.no_d7 and (B, H, W) == (8, 1080, 1920):
@@ -605,6 +608,40 @@ def cpu_model_name():
   except OSError:
     pass
   return "unknown"
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6
+
+
+def dump_outputs(d, engs, nn_cost):
+  """--dump-outputs: what the last timed step handed back, per stream -- the forward's six outputs (odt_read_outputs: boxes,
+  labels, probs, detections per frame, [M,256,7,7] RoI features, their 7x7 mean) and the step's last nn_matching cost matrix --
+  as DIR/<name>.npy (float32; the cost matrix float64, as the call returns it).  An array that would take the total past
+  DUMP_BUDGET_BYTES keeps a fixed, seeded sample of its rows, listed in DIR/<name>_rows.npy.  Returns {name: shape}."""
+  os.makedirs(d, exist_ok=True)
+  names = ("final_boxes", "final_labels", "final_probs", "final_valid_indices", "fpn_box_feat", "pooled")
+  arrays = []
+  for i, e in enumerate(engs):
+    pre = "stream%d_" % i if len(engs) > 1 else ""
+    got = e.read_outputs(want_feats=True, want_pooled=True)
+    arrays += [(pre + n, np.ascontiguousarray(a, dtype=np.float32)) for n, a in zip(names, got)]
+    if nn_cost[i] is not None:
+      arrays.append((pre + "nn_cosine_cost", np.ascontiguousarray(nn_cost[i], dtype=np.float64)))
+  hdr = 256                     # room for one .npy header
+  left, shapes = DUMP_BUDGET_BYTES, {}
+  for name, a in sorted(arrays, key=lambda na: na[1].nbytes):      # smallest first: only the largest ones are ever sampled
+    if a.nbytes + hdr > left:
+      row = max(1, a.nbytes // max(1, a.shape[0]))
+      rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(0, left - 2 * hdr) // (row + 8), replace=False))
+      a = a[rows]
+      path = os.path.join(d, name + "_rows.npy")
+      np.save(path, rows.astype(np.float64))
+      left -= os.path.getsize(path)
+    path = os.path.join(d, name + ".npy")
+    np.save(path, a)
+    left -= os.path.getsize(path)
+    shapes[name] = list(a.shape)
+  return shapes
 
 
 def verify_timed_region(engs, all_frames):

@@ -149,3 +149,38 @@ def test_bench_counter_csv_reader(tmp_path):
   is_h2 = lambda k: ("conv_h2" in k or "conv_stem" in k) and "kernel" in k and "split_weights" not in k
   assert bench.sum_counter_csv(str(p), "FETCH_SIZE", is_h2) == (1524.0, 2)
   assert bench.sum_counter_csv(str(p), "WRITE_SIZE", is_h2) == (3.0, 1)
+
+
+def test_bench_dump_outputs(tmp_path):
+  """bench.py --dump-outputs: one float .npy per output of the last timed step, labels / counts exact in float32, and the
+  total within 64 MB -- past it the largest arrays keep a seeded row sample (same rows on every run) with its row indices."""
+  import bench
+  rng = np.random.default_rng(1)
+
+  class Eng(object):
+    def __init__(self, M):
+      self.out = (rng.random((8, 100, 4), dtype=np.float32), rng.integers(0, 15, (8, 100)).astype(np.int32),
+                  rng.random((8, 100), dtype=np.float32), np.full(8, M // 8, np.int32),
+                  rng.random((M, 256, 7, 7), dtype=np.float32), rng.random((M, 256), dtype=np.float32))
+
+    def read_outputs(self, want_feats, want_pooled):
+      assert want_feats and want_pooled
+      return self.out
+
+  e = Eng(800)
+  shapes = bench.dump_outputs(str(tmp_path / "one"), [e], [np.ones((64, 100))])
+  assert shapes["fpn_box_feat"] == [800, 256, 7, 7] and shapes["nn_cosine_cost"] == [64, 100]
+  labels = np.load(str(tmp_path / "one" / "final_labels.npy"))
+  assert labels.dtype == np.float32 and np.array_equal(labels, e.out[1])
+  assert np.load(str(tmp_path / "one" / "nn_cosine_cost.npy")).dtype == np.float64
+  engs = [e, Eng(800)]
+  for run in ("a", "b"):
+    d = tmp_path / run
+    shapes = bench.dump_outputs(str(d), engs, [None, None])
+    files = os.listdir(str(d))
+    assert sum(os.path.getsize(str(d / f)) for f in files) <= 64 * 10**6
+    assert all(np.load(str(d / f)).dtype in (np.float32, np.float64) for f in files)
+  assert shapes["stream0_fpn_box_feat"] == [800, 256, 7, 7] and 0 < shapes["stream1_fpn_box_feat"][0] < 800
+  rows = np.load(str(tmp_path / "a" / "stream1_fpn_box_feat_rows.npy"))
+  assert np.array_equal(rows, np.load(str(tmp_path / "b" / "stream1_fpn_box_feat_rows.npy")))
+  assert np.array_equal(np.load(str(tmp_path / "a" / "stream1_fpn_box_feat.npy")), engs[1].out[4][rows.astype(np.int64)])

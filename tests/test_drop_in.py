@@ -4,12 +4,11 @@ obj_detect_tracking.py:505-517, :577-695).  These tests drive that exact call pa
 
 BASELINE config #1 ("plumbing"): the reference ships no test video and cv2/av are not
 installed, so the frame loop is driven by a synthetic in-memory reader exposing the
-cv2.VideoCapture methods the loop uses.  When /root/reference is present (build
-container) the UNMODIFIED reference Tracker consumes our Detections and our HIP-backed metric.
+cv2.VideoCapture methods the loop uses.  What the UNMODIFIED reference Tracker did with our
+Detections and our HIP-backed metric is recorded in tests/golden/lockstep_ref.npz (make_lockstep_golden.py).
 """
 import os
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -25,18 +24,9 @@ from object_detection_tracking_amd.deep_sort import (Detection, NearestNeighborD
 from object_detection_tracking_amd.weights import synthetic_frames
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF = "/root/reference"
-
-
-def _reference_tracker_cls():
-  if not os.path.isdir(os.path.join(REF, "deep_sort")):
-    return None
-  np.float = float; np.int = int          # numpy-2 removed the aliases the reference uses
-  sys.modules.setdefault("cv2", types.ModuleType("cv2"))
-  if REF not in sys.path:
-    sys.path.append(REF)
-  from deep_sort.tracker import Tracker
-  return Tracker
+if G not in sys.path:
+  sys.path.append(G)
+import make_lockstep_golden as golden  # noqa: E402
 
 
 class SyntheticCapture(object):
@@ -102,32 +92,19 @@ def test_session_shim_multi(backend):
     m.close()
 
 
-def test_plumbing_video_loop_with_tracker(backend):
-  """config #1: frame loop (frame_gap) -> sess.run -> create_obj_infos -> tracker NMS ->
-  Tracker.predict/update, exactly the call sequence of obj_detect_tracking.py:577-695 -- on the simulator in the CPU
-  suite and on the product library under -m gpu (detector, cosine metric, native DeepSORT and TMOT cores all on hip)."""
-  emu_lib = backend[1]
-  Tracker = _reference_tracker_cls()
+def video_loop_detections(lib):
+  """config #1's frame loop (frame_gap) -> sess.run -> create_obj_infos -> tracker NMS, exactly the call sequence of
+  obj_detect_tracking.py:577-695: yields, per processed frame, the Detections of the top detection's class that the
+  trackers are handed (None for a frame without detections: the trackers are not called)."""
   cfg = small_config(resnet_num_block=[1, 1, 1, 1], rpn_test_post_nms_topk=32)
-  m = models.get_model(cfg, 0, weights=weights_for(cfg), lib=emu_lib)
+  m = models.get_model(cfg, 0, weights=weights_for(cfg), lib=lib)
   id2class = {i: n for i, n in enumerate(ACTEV_CLASSES)}
   base = synthetic_frames(1, 96, 128)[0]
   video = np.stack([np.roll(base, 2 * i, axis=1) for i in range(9)])
   vcap = SyntheticCapture(video)
   frame_gap, min_conf = 4, 0.02           # random-init weights: use a reachable confidence
-  metric = NearestNeighborDistanceMetric("cosine", 0.5, 5, lib=emu_lib)
-  tracker = Tracker(metric, max_iou_distance=0.5) if Tracker else None
-  # the native trackers on the same detections: DeepSORT core and the TMOT / JDE core
-  # (obj_detect_tracking_multi_queuer_tmot.py:543-583: (tlwh, conf, feature) triples)
-  from object_detection_tracking_amd.deep_sort import Tracker as NativeTracker
-  from object_detection_tracking_amd.tmot import BaseTrack, JDETracker
-  native = NativeTracker(NearestNeighborDistanceMetric("cosine", 0.5, 5, lib=emu_lib), max_iou_distance=0.5,
-                         lib=emu_lib)
-  BaseTrack._count = 0
-  jde = JDETracker(min_conf_jde := 0.02, frame_gap=4., lib=emu_lib)
-  n_jde = 0
   sess = models.Session()
-  cur_frame, n_runs, n_det = 0, 0, 0
+  cur_frame = 0
   try:
     while cur_frame < int(vcap.get(7)):
       suc, frame = vcap.read()
@@ -141,55 +118,73 @@ def test_plumbing_video_loop_with_tracker(backend):
           [m.final_boxes, m.final_labels, m.final_probs, m.fpn_box_feat],
           feed_dict=m.get_feed_dict_forward(im))
       assert len(feats) == len(boxes)
-      n_runs += 1
-      objs = [id2class[int(l)] for l in labels[:1]]        # class of the top detection
-      for obj in objs:
+      if len(labels) == 0:
+        yield None
+      else:
+        obj = id2class[int(labels[0])]                 # class of the top detection
         dets = create_obj_infos(cur_frame, boxes, probs, labels, feats, id2class, [obj], min_conf,
                                 0, scale)
         keep = preprocessing.non_max_suppression(np.array([d.tlwh for d in dets]).reshape(-1, 4),
                                                  0.85, np.array([d.confidence for d in dets]))
-        dets = [dets[i] for i in keep]
-        n_det += len(dets)
-        assert all(isinstance(d, Detection) and d.feature.shape == (256,) for d in dets)
-        if tracker is not None and obj == objs[0]:
-          tracker.predict()
-          tracker.update(dets)
-        if obj == objs[0]:
-          native.predict(); native.update(dets)
-          out = jde.update([(d.tlwh.copy(), d.confidence, d.feature.copy()) for d in dets])
-          n_jde += len(out)
-          if tracker is not None:              # native DeepSORT core == reference tracker on live detections
-            assert [t.track_id for t in tracker.tracks] == [t.track_id for t in native.tracks]
+        yield [dets[i] for i in keep]
       cur_frame += 1
   finally:
     m.close()
+
+
+def test_plumbing_video_loop_with_tracker(backend):
+  """config #1: video_loop_detections -> Tracker.predict/update -- on the simulator in the CPU suite and on the product
+  library under -m gpu (detector, cosine metric, native DeepSORT and TMOT cores all on hip).  On the simulator, where the
+  golden record was made, the native DeepSORT core's track ids equal the reference Tracker's after every update."""
+  name, emu_lib = backend
+  # the native trackers on the same detections: DeepSORT core and the TMOT / JDE core
+  # (obj_detect_tracking_multi_queuer_tmot.py:543-583: (tlwh, conf, feature) triples)
+  from object_detection_tracking_amd.deep_sort import Tracker as NativeTracker
+  from object_detection_tracking_amd.tmot import BaseTrack, JDETracker
+  native = NativeTracker(NearestNeighborDistanceMetric("cosine", 0.5, 5, lib=emu_lib), max_iou_distance=0.5,
+                         lib=emu_lib)
+  BaseTrack._count = 0
+  jde = JDETracker(min_conf_jde := 0.02, frame_gap=4., lib=emu_lib)
+  ref_ids = golden.unpack(np.load(os.path.join(G, "lockstep_ref.npz")), "vl_ids") if name == "emu" else None
+  n_jde = n_runs = n_det = n_upd = 0
+  for dets in video_loop_detections(emu_lib):
+    n_runs += 1
+    if dets is None:
+      continue
+    n_det += len(dets)
+    assert all(isinstance(d, Detection) and d.feature.shape == (256,) for d in dets)
+    native.predict(); native.update(dets)
+    out = jde.update([(d.tlwh.copy(), d.confidence, d.feature.copy()) for d in dets])
+    n_jde += len(out)
+    if ref_ids is not None:              # native DeepSORT core == reference tracker on live detections
+      assert [t.track_id for t in native.tracks] == list(ref_ids[n_upd]), n_runs
+    n_upd += 1
   assert n_runs == 3
   assert n_det > 0
-  if tracker is not None:
-    assert len(tracker.tracks) > 0
+  if ref_ids is not None:
+    assert len(ref_ids) == n_upd and len(ref_ids[-1]) > 0
   assert len(native.tracks) > 0
   assert n_jde > 0 and all(t.track_id >= 1 for t in jde.tracked_stracks)
 
 
-def test_reference_tracker_with_hip_metric_reproduces_golden_tracks(emu_lib):
-  """The unmodified reference Tracker + our metric class == the reference end to end."""
-  Tracker = _reference_tracker_cls()
-  if Tracker is None:
-    pytest.skip("/root/reference not present (GPU box)")
-  g = np.load(os.path.join(G, "deep_sort_ref.npz"))
-  tracker = Tracker(NearestNeighborDistanceMetric("cosine", 0.5, budget=5, lib=emu_lib),
-                    max_iou_distance=0.5)
-  o = t = 0
-  for fr, (n, nt) in enumerate(zip(g["seq_n"], g["seq_tracks_n"])):
-    dets = [Detection(g["seq_tlwh"][o + i], 0.95, g["seq_feat"][o + i]) for i in range(n)]
-    o += n
-    tracker.predict(); tracker.update(dets)
-    got = np.asarray([[tr.track_id] + list(tr.to_tlwh()) for tr in tracker.tracks
-                      if tr.is_confirmed() and tr.time_since_update <= 1]).reshape(-1, 5)
-    want = g["seq_tracks"][t:t + nt]; t += nt
-    assert got.shape == want.shape, fr
-    assert np.array_equal(got[:, 0], want[:, 0]), fr
-    np.testing.assert_allclose(got[:, 1:], want[:, 1:], rtol=1e-9, atol=1e-6)
+def test_hip_metric_replays_reference_tracker_calls(emu_lib):
+  """Our metric class under the unmodified reference Tracker: every partial_fit / distance call that Tracker makes on the
+  deep_sort_ref.npz sequence (recorded in lockstep_ref.npz), replayed on our metric, gives the reference metric's cost
+  matrices -- so the reference Tracker driving our metric reproduces the reference's track table."""
+  g = np.load(os.path.join(G, "lockstep_ref.npz"))
+  feat, tgt, act, cost = (golden.unpack(g, "mc_" + k) for k in ("feat", "targets", "active", "cost"))
+  met = NearestNeighborDistanceMetric("cosine", 0.5, budget=5, lib=emu_lib)
+  assert met.matching_threshold == 0.5
+  ndist = 0
+  for k, kind in enumerate(g["mc_kind"]):
+    if kind == 0:
+      met.partial_fit(feat[k], tgt[k], list(act[k]))
+    else:
+      got = met.distance(feat[k], list(tgt[k]))
+      assert got.shape == (len(tgt[k]), len(feat[k])), k
+      np.testing.assert_allclose(got.reshape(-1), cost[k], rtol=0, atol=1e-5, err_msg=str(k))
+      ndist += 1
+  assert ndist > 10 and (g["mc_kind"] == 0).sum() == len(np.load(os.path.join(G, "deep_sort_ref.npz"))["seq_n"])
 
 
 def test_metric_class_bookkeeping():

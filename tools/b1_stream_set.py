@@ -1,6 +1,5 @@
 """Tuning aid: b = 1 frames in flight on predict_stream's handles (replicas without side streams), K = 1 .. 4, device-resident."""
 import os, sys, time, json
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from object_detection_tracking_amd import models

@@ -1,6 +1,5 @@
 """EfficientDet-D7 @1536 (config #5) with K consecutive frames in flight on K handles (one stream each), device-resident frames."""
 import os, sys, time, json
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from object_detection_tracking_amd import models
