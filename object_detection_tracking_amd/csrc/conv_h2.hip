@@ -473,26 +473,11 @@ int launch_conv_h2(const ConvParams& p, const ConvParams* dev, hipStream_t strea
   const long M = (long)p.B * p.Ho * p.Wo;
   const int bn = p.wt_split_bn;
   const int bm = p.wt_split_bm;
-  ODT_CHECK(((bm == 256 && (bn >= 128 || p.wt_split_kwr)) || (bm == 128 && bn <= 128 && !p.wt_split_kwr) ||
-             (bm == 512 && bn == 64 && (!p.wt_split_kwr || p.Ho * p.Wo >= 512)) || (bm == 64 && (bn == 128 || bn == 64) && !p.wt_split_kwr)) && (bn == 256 || bn == 128 || bn == 64) && p.Cin % 32 == 0 && p.kh * p.kw <= 32 && p.in_amax != nullptr &&
-            p.h2_chinv != nullptr && (p.in2 == nullptr || (p.in2_amax != nullptr && p.Cin2 % 32 == 0)) && p.nlvl <= 1,
-            "conv h2: unsupported tile / shape, or no recorded input range");
   const int sk = p.splitk > 1 ? p.splitk : 1;
-  ODT_CHECK(sk == 1 || (p.partial != nullptr && p.in2 == nullptr && p.head_wt == nullptr && (p.kh * p.kw * p.Cin >> 5) >= sk),
-            "conv h2: split-K needs a partial buffer, a single source and at least one stage per range");
   const unsigned grid = (unsigned)(((M + bm - 1) / bm) * (cout_padded(p.Cout) / bn) * sk);
   if (p.wt_split_kwr) {
-    ODT_CHECK(p.kw == 3 && p.stride == 1 && p.in_Wa == p.Wo && p.in2 == nullptr && 2 * p.dil <= 4 &&
-              (sk == 1 || (bm == 256 && bn >= 128 && p.f_wt == nullptr && p.kh * (p.Cin >> 5) >= sk)), "conv h2k: unsupported shape");
-    ODT_CHECK(p.f_wt == nullptr || (bm == 256 && bn == p.Cout && (bn == 256 || bn == 128 || bn == 64) && p.head_wt == nullptr && p.res_mode == 0 && p.relu <= 1 && p.f_cout % 32 == 0 &&
-                                    p.f_cout > 0 && p.f_cout <= 1024 && p.f_out != nullptr && p.f_chinv != nullptr && p.f_bias != nullptr && p.f_out_ldc % 4 == 0 &&
-                                    (p.f_res == nullptr || p.f_res_ldc % 4 == 0) && (double)M * p.f_out_ldc * 4.0 < 2147483648.0 &&
-                                    (p.f_res == nullptr || (double)M * p.f_res_ldc * 4.0 < 2147483648.0)),
-              "conv h2k: unsupported fused 1x1 tail");
     launch_conv_h2k(p, dev, grid, stream);
-  } else if (p.f_wt != nullptr) {
-    ODT_CHECK(false, "conv h2: a fused 1x1 tail needs the kw-reuse kernel");
-  } else if (bm == 64 && conv_h2d_fits(p) && !env_knob_off(K_CONV_H2_BK64)) {
+  } else if (bm == 64 && p.h2_bk64) {
     // the dense 1x1 reductions on two-wave tiles: double stages (conv_h2d.hip; ODT_CONV_H2_BK64=0: the single-stage kernel, A/B)
     launch_conv_h2d(p, dev, grid, stream);
   } else if (bm == 64 && bn == 64) {         // ... 64 x 64 tiles: twice the workgroups again (latency-bound reductions at b = 1)

@@ -84,8 +84,8 @@ bool conv_split_supported(const ConvParams& p) {
 
 // ---- policy: which convs take the split kernels, and which family.  A model's policy is fixed when its handle is
 // created (odt_config.conv_arith / conv_split_family -> odt_create) and recorded with the handle (odt_describe); the
-// ODT_CONV_* environment variables are debug / A-B overrides on top of it, read ONCE per handle -- and per call only by
-// the stand-alone test entry points (odt_op_conv2d ...), which have no handle.
+// ODT_CONV_* overrides (debug / A-B) of the handle's knob snapshot go on top of it (conv_policy_with_knobs) -- or those of
+// the call for the stand-alone test entry points (odt_op_conv2d ...), which have no handle.
 ConvPolicy conv_policy_default() {
   ConvPolicy q;
   q.arith = 1;            // bf16x3 split where it pays (same-box A/B at b=8 1080p: 116 -> 178 FPS, parity suite green)
@@ -110,9 +110,9 @@ ConvPolicy conv_policy_default() {
   return q;
 }
 
-ConvPolicy conv_policy_from_env(ConvPolicy q) {
+ConvPolicy conv_policy_with_knobs(ConvPolicy q, const Knobs& kn) {
   auto geti = [&](Knob k, long* dst) {
-    const KnobVal& e = env_knob(k);
+    const KnobVal& e = kn.get(k);
     if (e.set) *dst = e.i;
   };
   long v;

@@ -648,11 +648,7 @@ static void launch_split3(const ConvParams& p, const ConvParams* dev, unsigned g
 
 void launch_split_reduce(const ConvParams& p, const ConvParams* dev, hipStream_t stream) {
   const long chunks = (long)p.B * p.Ho * p.Wo * (cout_padded(p.Cout) / 4);
-  const long blocks = (chunks + 255) / 256;
-  // at most two blocks per CU (grid-stride; same-box A/B at b = 1: 2048 blocks 150.4, 512 167.5, 256 166.8, 128 159.6 FPS): every block ends with a conditional atomicMax on the ONE range slot of the output,
-  // and the blocks of a short pass all find the slot empty -- 2040 same-address atomics serialised in L2 made this pass 35 us
-  // per call at b = 1 (1.2 ms of the 6.8 ms frame, profiles/r04_kernel_stats_bench_b1_single_before.txt)
-  const long capv = env_knob_long(K_SPLIT_REDUCE_BLOCKS, 512L), cap = capv > 0 ? capv : 512L;
+  const long blocks = (chunks + 255) / 256, cap = p.reduce_blocks;     // (grid-stride; conv_finish sets the cap)
   hipLaunchKernelGGL(split_reduce_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, stream, dev);
 }
 
@@ -660,14 +656,9 @@ int launch_conv_split3(const ConvParams& p, const ConvParams* dev, hipStream_t s
   const long M = (long)p.B * p.Ho * p.Wo;
   const int bn = p.wt_split_bn != 0 ? p.wt_split_bn : conv_split_bn(p.Cout);
   const int bm = p.wt_split_bm;
-  ODT_CHECK((bm == 256 || (bm == 128 && bn >= 128)) && p.Cin % 16 == 0 && p.kh * p.kw <= 32, "conv split3: unsupported tile / shape");
   const int sk = p.splitk > 1 ? p.splitk : 1;
-  ODT_CHECK(sk == 1 || (p.partial != nullptr && p.in2 == nullptr && (p.kh * p.kw * p.Cin >> 4) >= sk),
-            "conv split3: split-K needs a partial buffer, a single source and at least one stage per range");
   const unsigned grid = (unsigned)(((M + bm - 1) / bm) * (cout_padded(p.Cout) / bn) * sk);
   if (p.wt_split_kwr) {
-    ODT_CHECK(bm == 256 && sk == 1 && p.kw == 3 && p.stride == 1 && p.in_Wa == p.Wo && p.in2 == nullptr,
-              "conv split3k: unsupported shape");
     if (bn == 256) {
       if (p.trace != nullptr) hipLaunchKernelGGL((conv_split3k_kernel<4, true>), dim3(grid), dim3(512), 0, stream, dev);
       else hipLaunchKernelGGL((conv_split3k_kernel<4, false>), dim3(grid), dim3(512), 0, stream, dev);

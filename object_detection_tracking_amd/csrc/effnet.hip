@@ -400,49 +400,42 @@ int launch_preprocess_rgb_resize(const void* frames, int dtype, int B, int Hs, i
   return 0;
 }
 
-namespace {
 constexpr int kDwPX2 = 2;
-// outputs per thread along x at stride 1: 8 (k = 5: 10.6 loads per output against 16.3 at 4; D7 same-box A/B 66.7 -> 67.6
-// FPS); ODT_DW_PX=4 is the A/B knob (knobs.hpp)
-int dw_px1() {
-  return env_knob_long(K_DW_PX, 8) == 4 ? 4 : 8;
-}
-}  // namespace
 
 static int dwconv_cblocks(const DwConvParams& p) { return ((p.ldc >> 2) + 15) / 16; }
 
-// pixel splits: one or two output blocks per thread (16 pixel groups per workgroup), at most 4096 workgroups in all
-int dwconv_splits(const DwConvParams& p) {
-  const int px = p.stride == 1 ? dw_px1() : kDwPX2;
-  const long units = (long)((p.Wo + px - 1) / px) * p.Ho;
-  // (with the fused squeeze every split is a partial sum the fold kernel has to add up: at most 1024 of them)
-  const long sumcap = env_knob_long(K_DW_SUMCAP, 2048L);   // A/B knob (1024 ... 8192: +-0.5 %)
-  const long cap = std::max<long>(1, (p.sum_part != nullptr ? sumcap : 4096) / ((long)dwconv_cblocks(p) * p.B));
-  return (int)std::max<long>(1, std::min(std::min<long>(cap, 1024), (units + 15) / 16));
-}
-
-int launch_dwconv(const DwConvParams& p0, hipStream_t stream) {
-  ODT_CHECK(p0.ldc % 4 == 0 && (p0.k == 3 || p0.k == 5) && (p0.stride == 1 || p0.stride == 2), "dwconv: bad geometry");
-  DwConvParams p = p0;
+int dwconv_plan(DwConvParams& p, bool squeeze, const Knobs& k) {
+  ODT_CHECK(p.ldc % 4 == 0 && (p.k == 3 || p.k == 5) && (p.stride == 1 || p.stride == 2), "dwconv: bad geometry");
   if (p.nlvl > 0) {
     // several maps in one launch: splits sized for the largest map (the others' surplus workgroups find nothing to do)
-    ODT_CHECK(p.nlvl <= 5 && p.B == 1 && p.stride == 1 && p.sum_part == nullptr, "dwconv: multi-map launches are batch 1, stride 1");
+    ODT_CHECK(p.nlvl <= 5 && p.B == 1 && p.stride == 1 && !squeeze, "dwconv: multi-map launches are batch 1, stride 1");
     int big = 0;
     for (int i = 1; i < p.nlvl; ++i) if ((long)p.lH[i] * p.lW[i] > (long)p.lH[big] * p.lW[big]) big = i;
     p.H = p.Ho = p.lH[big]; p.W = p.Wo = p.lW[big];
   }
-  p.cqn = 16; p.nsplit = dwconv_splits(p);
-  const bool bands = !env_knob_off(K_DW_XCD);     // A/B knob
-  p.xcd_bands = bands ? 1 : 0;
+  // outputs per thread along x at stride 1: 8 (k = 5: 10.6 loads per output against 16.3 at 4; D7 same-box A/B 66.7 -> 67.6
+  // FPS); ODT_DW_PX=4 is the A/B knob (knobs.hpp)
+  p.px = p.stride == 1 ? (k.get_long(K_DW_PX, 8) == 4 ? 4 : 8) : kDwPX2;
+  // pixel splits: one or two output blocks per thread (16 pixel groups per workgroup), at most 4096 workgroups in all
+  const long units = (long)((p.Wo + p.px - 1) / p.px) * p.Ho;
+  // (with the fused squeeze every split is a partial sum the fold kernel has to add up: at most 1024 of them)
+  const long sumcap = k.get_long(K_DW_SUMCAP, 2048L);   // A/B knob (1024 ... 8192: +-0.5 %)
+  const long cap = std::max<long>(1, (squeeze ? sumcap : 4096) / ((long)dwconv_cblocks(p) * p.B));
+  p.cqn = 16;
+  p.nsplit = (int)std::max<long>(1, std::min(std::min<long>(cap, 1024), (units + 15) / 16));
+  p.xcd_bands = k.off(K_DW_XCD) ? 0 : 1;     // A/B knob
+  return 0;
+}
+
+int launch_dwconv(const DwConvParams& p, hipStream_t stream) {
   const dim3 g(dwconv_cblocks(p), p.nsplit, p.nlvl > 0 ? p.nlvl : p.B), t(256);
-  const bool wide = dw_px1() == 8;
   if (p.k == 3 && p.stride == 1) {
-    if (wide) hipLaunchKernelGGL((dwconv_kernel<3, 1, 8>), g, t, 0, stream, p);
+    if (p.px == 8) hipLaunchKernelGGL((dwconv_kernel<3, 1, 8>), g, t, 0, stream, p);
     else hipLaunchKernelGGL((dwconv_kernel<3, 1, 4>), g, t, 0, stream, p);
   } else if (p.k == 3) {
     hipLaunchKernelGGL((dwconv_kernel<3, 2, kDwPX2>), g, t, 0, stream, p);
   } else if (p.stride == 1) {
-    if (wide) hipLaunchKernelGGL((dwconv_kernel<5, 1, 8>), g, t, 0, stream, p);
+    if (p.px == 8) hipLaunchKernelGGL((dwconv_kernel<5, 1, 8>), g, t, 0, stream, p);
     else hipLaunchKernelGGL((dwconv_kernel<5, 1, 4>), g, t, 0, stream, p);
   } else {
     hipLaunchKernelGGL((dwconv_kernel<5, 2, kDwPX2>), g, t, 0, stream, p);

@@ -2,7 +2,6 @@
 #include "knobs.hpp"
 
 #include <cstdlib>
-#include <mutex>
 
 namespace odt {
 namespace {
@@ -13,38 +12,21 @@ const char* const kNames[K_COUNT] = {
 #undef ODT_KNOB_NAME
 };
 
-struct Table {
-  KnobVal v[K_COUNT];
-  std::string text[K_COUNT];
-  Table() { read(); }
-  void read() {
-    for (int k = 0; k < K_COUNT; ++k) {
-      const char* e = getenv(kNames[k]);
-      KnobVal n;
-      if (e != nullptr) { n.set = true; n.i = atol(e); n.d = atof(e); n.c0 = e[0]; text[k] = e; } else text[k].clear();
-      v[k] = n;
-    }
-  }
-};
-
-std::mutex g_mu;
-Table& table() { static Table t; return t; }
-
 }  // namespace
 
-const KnobVal& env_knob(Knob k) { return table().v[k]; }
-
-void knobs_reload() {
-  std::lock_guard<std::mutex> lk(g_mu);
-  table().read();
+Knobs knobs_read() {
+  Knobs t;
+  for (int k = 0; k < K_COUNT; ++k) {
+    const char* e = getenv(kNames[k]);
+    if (e != nullptr) { t.v[k].set = true; t.v[k].i = atol(e); t.v[k].d = atof(e); t.v[k].c0 = e[0]; t.text[k] = e; }
+  }
+  return t;
 }
 
-std::vector<std::string> knobs_active() {
-  std::lock_guard<std::mutex> lk(g_mu);
+std::vector<std::string> Knobs::active() const {
   std::vector<std::string> out;
-  const Table& t = table();
   for (int k = 0; k < K_COUNT; ++k)
-    if (t.v[k].set) out.push_back(std::string(kNames[k]) + "=" + t.text[k]);
+    if (v[k].set) out.push_back(std::string(kNames[k]) + "=" + text[k]);
   return out;
 }
 

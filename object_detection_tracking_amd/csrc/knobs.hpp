@@ -1,8 +1,8 @@
 // The ODT_* environment overrides: A/B and test knobs, none needed in production.
-// knobs.cpp is the ONLY reader of the process environment.  The table is re-read when a handle / tracker / cosine context is
-// created and at the stand-alone odt_op_* entry points (knobs_reload); plan builders and launchers ask env_knob() -- a plain
-// array read, no getenv on any launch path -- and every handle remembers which variables were set when it was created:
-// odt_describe lists them by name ("env_overrides") and counts them ("env_overrides_applied").
+// knobs.cpp is the ONLY reader of the process environment.  knobs_read() takes an immutable snapshot (Knobs) at a few
+// capture points: a handle's at odt_finalize_weights (the plan is built from it and odt_describe lists its overrides by
+// name, "env_overrides"), a tracker's / cosine context's at its creation, a stand-alone odt_op_* call's at the call.
+// Every choice a knob makes is recorded in the plan's op / conv records when they are made; launchers read records only.
 #pragma once
 #include <string>
 #include <vector>
@@ -33,10 +33,14 @@ struct KnobVal {
   char c0 = 0;           // first character
 };
 
-const KnobVal& env_knob(Knob k);
-inline bool env_knob_off(Knob k) { const KnobVal& v = env_knob(k); return v.set && v.c0 == '0'; }     // "NAME=0"
-inline long env_knob_long(Knob k, long dflt) { const KnobVal& v = env_knob(k); return v.set ? v.i : dflt; }
-void knobs_reload();                              // re-read the environment (creation paths and odt_op_* only)
-std::vector<std::string> knobs_active();          // "ODT_NAME=value" of every variable that is set, table order
+struct Knobs {
+  KnobVal v[K_COUNT];
+  std::string text[K_COUNT];
+  const KnobVal& get(Knob k) const { return v[k]; }
+  bool off(Knob k) const { return v[k].set && v[k].c0 == '0'; }                  // "NAME=0"
+  long get_long(Knob k, long dflt) const { return v[k].set ? v[k].i : dflt; }
+  std::vector<std::string> active() const;        // "ODT_NAME=value" of every variable that is set, table order
+};
+Knobs knobs_read();                               // the environment as it is now
 
 }  // namespace odt

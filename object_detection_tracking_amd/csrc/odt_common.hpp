@@ -134,15 +134,23 @@ struct ConvParams {
   // conv0 + pool0 in one kernel (conv_stem.hip; fuse_stem): `out` is the 3x3 / stride-2 max-pooled map [B, out_H, out_W, out_ldc]
   // of the conv's [B, Ho, Wo, Cout] result, which is not written
   int stem_pool;
+  // launch choices (conv_finish; the launchers read these, never a knob)
+  int f32_tile, f32_stages, f32_fine;   // exact-f32 kernel: 1 128x64 | 2 64x64 | 3 128x128 tile; LDS stages; fine-grained loop
+  int h2_bk64;         // two-wave dense 1x1 fp16x2 tiles on conv_h2d_kernel (conv_h2d_fits; ODT_CONV_H2_BK64=0: off)
+  int reduce_blocks;   // block cap of the split-K combine pass (ODT_SPLIT_REDUCE_BLOCKS)
 };
-// fills the derived fields (multiply-shift divisors); call before copying a record to the device
+// fills the derived fields (multiply-shift divisors)
 void conv_prepare(ConvParams& p);
-// dev_params: device copy of `p` (plan-owned); nullptr = stage a temporary (stand-alone calls)
-int launch_conv(const ConvParams& p, hipStream_t stream, const ConvParams* dev_params = nullptr);
+// finishes a record: conv_prepare, the ODT_CONV_DEBUG bits and every launch choice above, then conv_check; once per record,
+// before it is copied to the device (the plan's upload_conv_records, the stand-alone conv calls)
+int conv_finish(ConvParams& p, const Knobs& k);
+int conv_check(const ConvParams& p);      // the launch preconditions of a record (shape, 32-bit offsets, split kernel family)
+// dispatch of a finished, checked record; dev: its device copy (the kernels read their parameters from there)
+int launch_conv(const ConvParams& p, const ConvParams* dev, hipStream_t stream);
 double conv_flops(const ConvParams& p);   // algorithmic 2*M*N*K
 // bf16x3 split path (conv_split.hip).  ConvPolicy: which convs take it and which kernel family -- per handle, fixed at
-// odt_create from odt_config (+ ODT_CONV_* debug overrides, conv_policy_from_env); the stand-alone test entry points
-// resolve it per call.
+// plan build from odt_config and the handle's ODT_CONV_* overrides (conv_policy_with_knobs); a stand-alone conv call
+// resolves it under the call's knobs.
 struct ConvPolicy {
   int arith;            // 0 exact-f32 MFMA everywhere | 1 bf16x3 split kernels where they pay
   int family;           // split kernel families allowed: 1 one-stage only | 3 + conv_split3_kernel where it fits | 2 + the
@@ -166,7 +174,7 @@ struct ConvPolicy {
   bool src2, res2;      // take the K-concatenated stage-entry convs / the 2x-upsampled-residual FPN laterals
 };
 ConvPolicy conv_policy_default();
-ConvPolicy conv_policy_from_env(ConvPolicy q);
+ConvPolicy conv_policy_with_knobs(ConvPolicy q, const Knobs& k);
 bool conv_split_supported(const ConvParams& p);
 // the layer is supported AND large enough to fill the chip with the split tiles
 bool conv_split_wanted(const ConvParams& p, const ConvPolicy& q);
@@ -195,6 +203,7 @@ size_t conv_h2f_weight_bytes(int Cout, int K);
 const float* conv_h2f_chinv(const void* img, int Cout, int K);
 int conv_make_h2f_weights(const float* wt, int Cout, int K, void* img_dev, hipStream_t stream);
 bool conv_stem_fits(const ConvParams& p);          // conv_stem.hip: the plan's conv0 on the fp16x2 family
+bool conv_h2d_fits(const ConvParams& p);           // conv_h2d.hip: double-stage two-wave tiles for the dense 1x1 fp16x2 layers
 int launch_conv_stem(const ConvParams& p, const ConvParams* dev, hipStream_t stream);
 bool conv_h2f_fusable(const ConvParams& a, const ConvParams& b);   // a: the KH x 3 producer, b: the 1x1 conv reading a.out
 size_t conv_split_partial_bytes(const ConvParams& p);   // scratch a split-K conv needs (0: none)
@@ -218,18 +227,21 @@ struct DwConvParams {
   int act;             // 0 none | 2 swish
   // optional fused squeeze (MBConv): per-workgroup sums of the OUTPUT per (image, channel) for the squeeze-excite gate,
   // sum_part[b][split][c] (fixed order); channel_mean_fold_kernel (launch_se_gate_from_parts) adds the splits
-  float* sum_part;     // [B][dwconv_splits()][ldc] or nullptr
-  int cqn, nsplit;     // filled by launch_dwconv: channel quads per workgroup (16), pixel splits
-  int xcd_bands;       // filled by launch_dwconv: 1 = contiguous band of workgroups per XCD (halo rows shared in its L2)
+  float* sum_part;     // [B][nsplit][ldc] or nullptr
+  int cqn, nsplit;     // filled by dwconv_plan: channel quads per workgroup (16), pixel splits
+  int xcd_bands;       // filled by dwconv_plan: 1 = contiguous band of workgroups per XCD (halo rows shared in its L2)
   // optional: several independent [H,W] maps in one launch (batch 1, stride 1 'SAME': the five pyramid levels of a class /
   // box net layer): map i reads lin[i] and writes lout[i], both [lH[i], lW[i], ldc]; grid z = map
   int nlvl;            // 0: off
   const float* lin[5];
   float* lout[5];
   int lH[5], lW[5];
+  int px;              // filled by dwconv_plan: outputs per thread along x (the kernel variant)
 };
+// fills cqn / nsplit / px / xcd_bands (squeeze: sum_part will be set -- sized [B][nsplit][ldc]) and checks the geometry;
+// multi-map records take the largest map's extent
+int dwconv_plan(DwConvParams& p, bool squeeze, const Knobs& k);
 int launch_dwconv(const DwConvParams& p, hipStream_t stream);
-int dwconv_splits(const DwConvParams& p);       // pixel splits launch_dwconv will use (sizes sum_part)
 // MBConv front half in one kernel (effnet_mbconv.hip): expand 1x1 + BN + swish -> depthwise k x k + BN + swish (+ squeeze
 // partial sums); the expanded tensor stays in LDS
 struct MbExpandDwParams {
@@ -399,6 +411,7 @@ int launch_nn_cosine(const float* gallery, const int* seg, const int* blocks, in
                      int D, double* cost, hipStream_t stream);
 // host-to-host cosine nearest-neighbour call with persistent scratch and a stream of its own (tracker.hip)
 struct CosineCtx {
+  const Knobs knobs = knobs_read();   // the ODT_* overrides when the context was created (stream priority, timing)
   int device = -1;
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;

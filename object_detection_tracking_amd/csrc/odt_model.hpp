@@ -82,6 +82,7 @@ using namespace odt;      // (odt_model is the C ABI's global handle type)
 
 struct odt_model {
   odt_config cfg;
+  Knobs knobs;                       // ODT_* overrides: taken at odt_create, retaken at odt_finalize_weights to build the plan
   int device = 0;
   hipStream_t own_stream = nullptr;
   bool finalized = false;
@@ -127,8 +128,6 @@ struct odt_model {
   // tail overlap: the selection / ROIAlign / box-head / NMS kernels of forward i (a few dozen workgroups each,
   // ~2 ms per 8-frame step) run on a side stream under the backbone of forward i+1.  The next forward's FPN stage
   // (the first op that overwrites what the tail reads: P2..P5, the RPN outputs) waits for the previous tail.
-  std::vector<std::string> env_active;   // "ODT_NAME=value" of the overrides set when the handle's plan was built (odt_describe lists them)
-  bool knob_tail_overlap_off = false;
   int tail_overlap = -1;             // -1 undecided | 0 off | 1 on (ODT_TAIL_OVERLAP=0 disables; own stream only)
   size_t op_first_fpn = 0, op_tail = 0;
   hipStream_t tail_stream = nullptr, done_stream = nullptr;
@@ -215,7 +214,7 @@ int upload_raw(odt_model* m, const std::vector<float>& v, const float** out);
 int add_conv(odt_model* m, const std::string& name, const Tensor& in, int cin, const float* wt, const float* bias, int kh,
              int kw, int cout, int stride, int dil, int pad_t, int pad_l, int Ho, int Wo, int oy, int ox, const Tensor* res,
              int res_mode, bool relu, int out_ldc, Tensor* out, const std::string& tap);
-int create_side_stream(hipStream_t* s);
+int create_side_stream(hipStream_t* s, const Knobs& k);
 ConvPolicy resolve_conv_policy(const odt_model* m);
 int attach_split_weights(odt_model* m);
 int fuse_rpn_heads(odt_model* m);

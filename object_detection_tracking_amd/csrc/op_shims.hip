@@ -23,8 +23,51 @@ int set_dev(int device) {
   ODT_HIP(hipGetDeviceCount(&n));
   ODT_CHECK(device >= 0 && device < n, "no such device");
   ODT_HIP(hipSetDevice(device));
-  knobs_reload();          // stand-alone ops (tests, tuning): the environment as it is at this call
   return 0;
+}
+
+// one stand-alone conv (odt_op_conv2d*: dense tensors, null stream) as a plan would run it: the library's policy under the
+// call's knobs, a temporary weight image / split-K scratch / input range where the split kernels take it, a finished record
+int run_conv(ConvParams q, const Knobs& kn) {
+  if (conv_check(q)) return 1;
+  conv_prepare(q);
+  struct Temps {                      // released on every path out of this function
+    void* img = nullptr; float* partial = nullptr; unsigned* amax = nullptr; ConvParams* rec = nullptr;
+    ~Temps() {
+      (void)hipStreamSynchronize(nullptr);
+      if (rec) (void)hipFree(rec);
+      if (img) (void)hipFree(img);
+      if (partial) (void)hipFree(partial);
+      if (amax) (void)hipFree(amax);
+    }
+  } tmp;
+  const ConvPolicy pol = conv_policy_with_knobs(conv_policy_default(), kn);
+  if (conv_split_wanted(q, pol)) {
+    const int Ksp = q.kh * q.kw * q.Cin + (q.in2 != nullptr ? q.Cin2 : 0);
+    ODT_HIP(hipMalloc(&tmp.img, conv_split_weight_bytes(q.Cout, Ksp)));
+    if (pol.family == 2 && q.in_amax == nullptr) {      // fp16x2 pieces need the sources' |max|: nobody recorded it for a stand-alone call
+      // (the scan covers the whole allocation B x in_Ha x in_Wa x in_ldc of a source: a stand-alone caller hands over
+      // dense tensors -- odt_op_conv2d* -- so this is the logical view; a sliced view would have to bring its own range)
+      ODT_HIP(hipMalloc((void**)&tmp.amax, 2 * kAmaxWays * sizeof(unsigned)));
+      ODT_HIP(hipMemsetAsync(tmp.amax, 0, 2 * kAmaxWays * sizeof(unsigned), nullptr));
+      if (launch_tensor_amax(q.in, (size_t)q.B * q.in_Ha * q.in_Wa * q.in_ldc, tmp.amax, nullptr)) return 1;
+      q.in_amax = tmp.amax;
+      if (q.in2 != nullptr) {
+        if (launch_tensor_amax(q.in2, (size_t)q.B * q.in2_Ha * q.in2_Wa * q.in2_ldc, tmp.amax + kAmaxWays, nullptr)) return 1;
+        q.in2_amax = tmp.amax + kAmaxWays;
+      }
+    }
+    conv_split_choose(q, pol);
+    if (conv_make_split_weights(q, tmp.img, nullptr)) return 1;
+    if (q.wt_split_kind == 2) q.h2_chinv = conv_h2_chinv(tmp.img, q.Cout, Ksp);
+    q.wt_split = tmp.img;
+    if (conv_split_partial_bytes(q) > 0) ODT_HIP(hipMalloc((void**)&tmp.partial, conv_split_partial_bytes(q)));
+    q.partial = tmp.partial;
+  }
+  if (conv_finish(q, kn)) return 1;
+  ODT_HIP(hipMalloc((void**)&tmp.rec, sizeof(ConvParams)));
+  ODT_HIP(hipMemcpy(tmp.rec, &q, sizeof(ConvParams), hipMemcpyHostToDevice));
+  return launch_conv(q, tmp.rec, nullptr);
 }
 
 }  // namespace
@@ -75,12 +118,13 @@ int odt_op_conv2d(int device, const float* in, int B, int H, int W, int Cin, con
   p.res_mode = p.res ? res_mode : 0; p.res_H = rH; p.res_W = rW; p.res_ldc = Cout; p.relu = relu;
   p.in_Ha = H; p.in_Wa = W;
   Tmp<unsigned long long> tr;
-  const bool trace = env_knob(K_CONV_TRACE).set;
+  const Knobs kn = knobs_read();      // (the environment as it is at this call)
+  const bool trace = kn.get(K_CONV_TRACE).set;
   const int max_blocks = 1 << 16;
   if (trace) { if (tr.alloc((size_t)max_blocks * 16) || tr.zero()) return 1; p.trace = tr.d; }
-  if (launch_conv(p, nullptr)) return 1;      // warm
+  if (run_conv(p, kn)) return 1;      // warm
   if (trace) { if (tr.zero()) return 1; }
-  if (launch_conv(p, nullptr)) return 1;
+  if (run_conv(p, kn)) return 1;
   ODT_HIP(hipDeviceSynchronize());
   if (trace) {   // tuning aid: per-phase wall-clock (100 MHz) statistics over the workgroups
     std::vector<unsigned long long> t((size_t)max_blocks * 16);
@@ -185,7 +229,7 @@ int odt_op_conv2d_cat(int device, const float* a, int B, int Ho, int Wo, int Ca,
   p.Ho = Ho; p.Wo = Wo; p.Cout = Cout; p.kh = 1; p.kw = 1; p.stride = 1; p.dil = 1;
   p.out_H = Ho; p.out_W = Wo; p.out_ldc = Cout; p.relu = relu;
   p.in2 = db2.d; p.Cin2 = Cb; p.in2_ldc = Cb; p.in2_Ha = Hb; p.in2_Wa = Wb; p.in2_stride = stride_b;
-  if (launch_conv(p, nullptr)) return 1;
+  if (run_conv(p, knobs_read())) return 1;
   ODT_HIP(hipDeviceSynchronize());
   return dout.get(out, nout);
 }
@@ -242,11 +286,11 @@ int odt_op_bottleneck_tail(int device, const float* in, int B, int H, int W, int
     a.f_out = dout.d; a.f_out_ldc = C3; a.f_cout = C3; a.f_relu = b.relu; a.f_out_amax = amax.d + 2 * kAmaxWays;
     a.out = nullptr; a.out_amax = nullptr;
     ConvParams recs[2] = {a, b};
-    if (rec.put(recs)) return 1;
+    if (conv_check(a) || rec.put(recs)) return 1;
     if (launch_conv_split(a, rec.d, nullptr)) return 1;
   } else {
     ConvParams recs[2] = {a, b};
-    if (rec.put(recs)) return 1;
+    if (conv_check(a) || conv_check(b) || rec.put(recs)) return 1;
     if (launch_conv_split(a, rec.d, nullptr) || launch_conv_split(b, rec.d + 1, nullptr)) return 1;
   }
   ODT_HIP(hipDeviceSynchronize());
@@ -287,9 +331,9 @@ int odt_op_stem(int device, const float* frame_pad, int B, int Hp, int Wp, const
     ODT_CHECK(conv_stem_fits(p), "odt_op_stem: shape not taken by the stem kernel");
     p.out = dout.d; p.out_H = Hq; p.out_W = Wq; p.stem_pool = 1;
     if (grid > 0) p.debug |= (grid & 0x3ff) << 20;
-    if (rec.put(&p) || launch_conv_split(p, rec.d, nullptr)) return 1;
+    if (conv_check(p) || rec.put(&p) || launch_conv_split(p, rec.d, nullptr)) return 1;
   } else {
-    if (rec.put(&p) || launch_conv_split(p, rec.d, nullptr)) return 1;
+    if (conv_check(p) || rec.put(&p) || launch_conv_split(p, rec.d, nullptr)) return 1;
     if (launch_maxpool3x3s2(dmap.d, B, Ho0, Wo0, 64, dout.d, Hq, Wq, nullptr)) return 1;
   }
   ODT_HIP(hipDeviceSynchronize());

@@ -163,8 +163,8 @@ int add_conv(odt_model* m, const std::string& name, const Tensor& in, int cin, c
 // lands on the main stream's queue is serialised behind the forward it is meant to overlap (seen with the tracker's
 // stream: tools/experiments/track_stream_collision.py); streams of another priority get queues of their own.
 // ODT_SIDE_STREAM_PRIORITY=0: plain streams (A/B).
-int create_side_stream(hipStream_t* s) {
-  const bool flat = env_knob_off(K_SIDE_STREAM_PRIORITY);
+int create_side_stream(hipStream_t* s, const Knobs& k) {
+  const bool flat = k.off(K_SIDE_STREAM_PRIORITY);
   if (flat) { ODT_HIP(hipStreamCreateWithFlags(s, hipStreamNonBlocking)); return 0; }
   int least = 0, greatest = 0;
   ODT_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -179,7 +179,7 @@ ConvPolicy resolve_conv_policy(const odt_model* m) {
   if (m->cfg.conv_arith == ODT_ARITH_F32) pol.arith = 0;
   else if (m->cfg.conv_arith == ODT_ARITH_BF16X3) pol.arith = 1;
   if (m->cfg.conv_split_family >= 1 && m->cfg.conv_split_family <= 3) pol.family = m->cfg.conv_split_family;
-  pol = conv_policy_from_env(pol);
+  pol = conv_policy_with_knobs(pol, m->knobs);
   // (the EfficientDet graph keeps the bf16x3 kernels: its convs mostly lack 256-row x 128-column tiles, and its in-place
   // gates would need their own range bookkeeping)
   if (m->cfg.graph == ODT_GRAPH_EFFNET && pol.family == 2) pol.family = 3;
@@ -225,7 +225,7 @@ int attach_split_weights(odt_model* m) {
       m->pre_amax = m->amax_dev + (size_t)(m->amax_used[0]++) * kAmaxWays;
       continue;
     }
-    if (op.kind == OP_ROI_HEAD && pol.family == 2 && m->roi_head.out_nhwc != nullptr && !env_knob_off(K_ROI_AMAX)) {
+    if (op.kind == OP_ROI_HEAD && pol.family == 2 && m->roi_head.out_nhwc != nullptr && !m->knobs.off(K_ROI_AMAX)) {
       // the box head's RoI features: ROIAlign records their range, so that fc6 (K = 12544, a third of the box head's time on the
       // bf16x3 kernels) can take the fp16x2 kernels like every other layer (round 6; ODT_ROI_AMAX=0: A/B)
       const int g = tail ? 1 : 0;
@@ -263,16 +263,16 @@ int attach_split_weights(odt_model* m) {
       // A/B at b=8 1080p 30.8 -> 29.8 ms of conv time, res4 conv1 275 -> 317 TF (profiles/r03_h2_nt_ab.txt; 4: large-output
       // stores, measured no gain).  ODT_CONV_NT overrides the mask (A/B).
       int nt = 3;
-      nt = (int)env_knob_long(K_CONV_NT, nt);
+      nt = (int)m->knobs.get_long(K_CONV_NT, nt);
       c.p.debug |= (nt & 7) << 10;
     }
     {
-      const bool per_wave = env_knob(K_AMAX_PER_WAVE).c0 == '1';
+      const bool per_wave = m->knobs.get(K_AMAX_PER_WAVE).c0 == '1';
       if (per_wave) c.p.debug |= 0x4000;      // A/B: range record per wave instead of per workgroup
     }
     if (c.p.wt_split_kind == 2) {
       c.p.h2_chinv = conv_h2_chinv(c.p.wt_split, c.p.Cout, K); ++m->convs_h2;
-      const bool norot = env_knob_off(K_CONV_H2_ROT);
+      const bool norot = m->knobs.off(K_CONV_H2_ROT);
       if (norot) c.p.debug |= 0x100;          // A/B: every workgroup walks the K slices in the same order
     }
     need_partial = std::max(need_partial, conv_split_partial_bytes(c.p));
@@ -326,7 +326,7 @@ int attach_split_weights(odt_model* m) {
 // ODT_FUSE_RPN_HEAD=0 keeps the two launches (A/B).  Called after attach_split_weights, before plan_arena.
 int fuse_rpn_heads(odt_model* m) {
   m->conv_fused.assign(m->convs.size(), 0);
-  if (env_knob_off(K_FUSE_RPN_HEAD)) return 0;
+  if (m->knobs.off(K_FUSE_RPN_HEAD)) return 0;
   const HostTensor* W = find_w(m, "__rpnhead/W");
   const HostTensor* Bv = find_w(m, "__rpnhead/b");
   if (W == nullptr || Bv == nullptr) return 0;
@@ -370,7 +370,7 @@ int fuse_rpn_heads(odt_model* m) {
 // attach_split_weights, before plan_arena.
 int fuse_bottleneck_tails(odt_model* m) {
   if (m->conv_fused.size() < m->convs.size()) m->conv_fused.resize(m->convs.size(), 0);
-  const char e0 = env_knob(K_FUSE_BOTTLENECK).c0;      // A/B: 0 off | 1 only the 256-wide blocks (res4) | 2 + the 128-wide (res3) | otherwise every fusable block
+  const char e0 = m->knobs.get(K_FUSE_BOTTLENECK).c0;      // A/B: 0 off | 1 only the 256-wide blocks (res4) | 2 + the 128-wide (res3) | otherwise every fusable block
   if (e0 == '0') return 0;
   const int min_cout = e0 == '1' ? 256 : (e0 == '2' ? 128 : 64);
   if (m->policy.arith == 0 || m->policy.family != 2) return 0;
@@ -405,7 +405,7 @@ int fuse_bottleneck_tails(odt_model* m) {
     ap.f_res = b.p.res_mode != 0 ? b.p.res : nullptr; ap.f_res_ldc = b.p.res_ldc;
     ap.f_out = b.p.out; ap.f_out_ldc = b.p.out_ldc; ap.f_cout = b.p.Cout; ap.f_relu = b.p.relu; ap.f_out_amax = b.p.out_amax;
     ap.debug |= b.p.debug & 0x400;           // the residual's non-temporal hint travels with it
-    if (env_knob_off(K_FUSE_ROT)) ap.debug |= 0x100;     // A/B: 0 = every workgroup walks the output column chunks in the same order
+    if (m->knobs.off(K_FUSE_ROT)) ap.debug |= 0x100;     // A/B: 0 = every workgroup walks the output column chunks in the same order
     ap.out = nullptr; ap.out_amax = nullptr;
     ob.skip = true;
     m->conv_fused[ob.conv] = 2;
@@ -421,7 +421,7 @@ int fuse_bottleneck_tails(odt_model* m) {
 // -- 1.07 GB written and read back at b=8 -- never exists).  Bit-identical.  ODT_FUSE_STEM=0 keeps the two launches (A/B).
 // Called after attach_split_weights, before plan_arena.
 int fuse_stem(odt_model* m) {
-  if (env_knob_off(K_FUSE_STEM)) return 0;
+  if (m->knobs.off(K_FUSE_STEM)) return 0;
   if (m->policy.arith == 0 || m->policy.family != 2) return 0;
   for (size_t oi = 0; oi + 1 < m->ops.size(); ++oi) {
     Op& oa = m->ops[oi]; Op& ob = m->ops[oi + 1];
@@ -441,7 +441,7 @@ int fuse_stem(odt_model* m) {
     // the conv map no longer exists: an arena handle must neither reserve memory for its stage name nor hand it out
     for (auto it = m->taps.begin(); it != m->taps.end();) { if (it->second.d == ap.out) it = m->taps.erase(it); else ++it; }
     ap.out = ob.out.d; ap.out_H = ob.out.H; ap.out_W = ob.out.W; ap.out_ldc = ob.out.C; ap.stem_pool = 1;
-    if (env_knob(K_STEM_GRID).set) ap.debug |= ((int)env_knob(K_STEM_GRID).i & 0x3ff) << 20;   // test knob: workgroups of the launch
+    if (m->knobs.get(K_STEM_GRID).set) ap.debug |= ((int)m->knobs.get(K_STEM_GRID).i & 0x3ff) << 20;   // test knob: workgroups of the launch
     ob.skip = true;
     m->stem_fused = 1;
   }
@@ -548,7 +548,8 @@ int plan_arena(odt_model* m) {
   return 0;
 }
 
-// conv parameter records in device memory (the kernels read their ConvParams from there).  The conv kernels address
+// conv parameter records in device memory (the kernels read their ConvParams from there), finished and checked here: every
+// launch choice is in the record, and the records do not change after this.  The conv kernels address
 // their tensors through buffer descriptors with 32-bit offsets: a launch whose input / output / residual tensor would
 // reach 2 GiB (b = 16 @1080p: conv0's output, the res2 tensors, P2) is cut into equal batch ranges, each with its own
 // record whose pointers start at that range's first image -- every image's arithmetic is unchanged.
@@ -568,9 +569,13 @@ static int conv_batch_chunks(const ConvParams& p, double limit) {
 
 int upload_conv_records(odt_model* m) {
   double limit = 2147483648.0;
-  if (env_knob(K_CONV_CHUNK_BYTES).d > 0) limit = env_knob(K_CONV_CHUNK_BYTES).d;
+  if (m->knobs.get(K_CONV_CHUNK_BYTES).d > 0) limit = m->knobs.get(K_CONV_CHUNK_BYTES).d;
   m->conv_recs.clear(); m->conv_rec0.clear(); m->conv_nrec.clear();
-  for (const ConvOp& c : m->convs) {
+  std::vector<char> launched(m->convs.size(), 0);
+  for (const Op& op : m->ops)
+    if (op.kind == OP_CONV && !op.skip) launched[op.conv] = 1;
+  for (size_t ci = 0; ci < m->convs.size(); ++ci) {
+    const ConvOp& c = m->convs[ci];
     const ConvParams& p = c.p;
     const int n = conv_batch_chunks(p, limit), bc = p.B / n;
     m->conv_rec0.push_back((int)m->conv_recs.size());
@@ -586,6 +591,7 @@ int upload_conv_records(odt_model* m) {
       if (p.head_out != nullptr) q.head_out = p.head_out + b0 * p.Ho * p.Wo * p.head_ldc;
       if (p.f_out != nullptr) q.f_out = p.f_out + b0 * p.Ho * p.Wo * p.f_out_ldc;
       if (p.f_res != nullptr) q.f_res = p.f_res + b0 * p.Ho * p.Wo * p.f_res_ldc;
+      if (launched[ci] && conv_finish(q, m->knobs)) { g_err = c.name + ": " + g_err; return 1; }
       m->conv_recs.push_back(q);
     }
     if (n > 1) ++m->chunked_convs;

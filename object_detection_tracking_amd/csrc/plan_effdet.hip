@@ -13,23 +13,23 @@ namespace odt {
 // channels) so that every 1x1 conv feeds conv_igemm_kernel; BN (epsilon 1e-3) is folded on the host.
 // channel stride of a tensor: padded with zero channels to a multiple of 32 -- or of 64 when the bf16x3 split kernels
 // take the 1x1 convs (their n-tile granule; conv_split.hip cout_padded)
-static bool eff_split_on() {        // (read per plan build: tests and A/B runs flip it inside one process)
-  return !env_knob_off(K_EFFDET_SPLIT);
+static bool eff_split_on(const odt_model* m) {
+  return !m->knobs.off(K_EFFDET_SPLIT);
 }
-int r32(int c) { return eff_split_on() ? (c + 63) / 64 * 64 : (c + 31) / 32 * 32; }
+static int r32(const odt_model* m, int c) { return eff_split_on(m) ? (c + 63) / 64 * 64 : (c + 31) / 32 * 32; }
 // squeeze-excite gate folded into the projection's weights at batch 1 (ODT_EFFDET_WSCALE=0: a pass over the activations)
 // MBConv front half (expand 1x1 -> depthwise) as one kernel, the expanded tensor kept in LDS (effnet_mbconv.hip):
 // ODT_EFFDET_FUSE_MB = 0 off | 1 (default) blocks whose depthwise output is at least 64 pixels on its short side (smaller
 // maps do not fill 16 x 16 patches: the halo / partial-tile recompute would cost more than the launch it saves) | 2 every block
-static int eff_fuse_mb_mode() {
-  return (int)env_knob_long(K_EFFDET_FUSE_MB, 1);
+static int eff_fuse_mb_mode(const odt_model* m) {
+  return (int)m->knobs.get_long(K_EFFDET_FUSE_MB, 1);
 }
-static int eff_fuse_mb_min() {           // A/B knob: smallest short side of the depthwise output that is fused in mode 1
-  const long v = env_knob_long(K_EFFDET_FUSE_MB_MIN, 64);
+static int eff_fuse_mb_min(const odt_model* m) {      // A/B knob: smallest short side of the depthwise output that is fused in mode 1
+  const long v = m->knobs.get_long(K_EFFDET_FUSE_MB_MIN, 64);
   return v > 0 ? (int)v : 64;
 }
-static bool eff_wscale_on() {
-  return !env_knob_off(K_EFFDET_WSCALE);
+static bool eff_wscale_on(const odt_model* m) {
+  return !m->knobs.off(K_EFFDET_WSCALE);
 }
 
 int eff_round_filters(int f, double width) {
@@ -134,12 +134,13 @@ int eff_sepconv(odt_model* m, const std::string& scope, const std::string& bn_sc
     op.dw.in = in.d; op.dw.wt = dwt; op.dw.bias = dbias; op.dw.out = t1.d;
     op.dw.B = B; op.dw.H = in.h; op.dw.W = in.w; op.dw.Ho = in.h; op.dw.Wo = in.w; op.dw.ldc = ldc;
     op.dw.k = 3; op.dw.stride = 1; op.dw.pad_t = 1; op.dw.pad_l = 1; op.dw.act = 0;
+    if (dwconv_plan(op.dw, false, m->knobs)) return 1;
     m->ops.push_back(op);
   }
   const float *wt, *bias;
   if (eff_upload_pw(m, scope, bn_scope, true, cin, ldc, cout, &wt, &bias, "pointwise_kernel")) return 1;
   // the pointwise bias variable of separable_conv2d is "<scope>/bias"
-  if (add_conv(m, scope, t1, ldc, wt, bias, 1, 1, cout, 1, 1, 0, 0, in.h, in.w, 0, 0, nullptr, 0, false, r32(cout), out, tap)) return 1;
+  if (add_conv(m, scope, t1, ldc, wt, bias, 1, 1, cout, 1, 1, 0, 0, in.h, in.w, 0, 0, nullptr, 0, false, r32(m, cout), out, tap)) return 1;
   m->convs.back().p.relu = act;
   return 0;
 }
@@ -147,7 +148,7 @@ int eff_sepconv(odt_model* m, const std::string& scope, const std::string& bn_sc
 int build_effdet_heads(odt_model* m, const Tensor* red, const int* red_ch) {
   const odt_config& cfg = m->cfg;
   const EffDetCfg dc = effdet_cfg(cfg.eff_det);
-  const int B = cfg.batch, F = dc.filters, LF = r32(F);
+  const int B = cfg.batch, F = dc.filters, LF = r32(m, F);
   const int ncls = cfg.num_class > 0 ? cfg.num_class : 90;
   // node sizes: utils.get_feat_sizes
   int fh[8], fw[8];
@@ -251,8 +252,8 @@ int build_effdet_heads(odt_model* m, const Tensor* red, const int* red_ch) {
   int off[6] = {0, 0, 0, 0, 0, 0};
   for (int l = 0; l < 5; ++l) off[l + 1] = off[l] + (fh[l + 3] * fw[l + 3] + 255) / 256 * 256;
   const int Mtot = off[5];
-  bool merge = B == 1 && eff_split_on();
-  merge = merge && !env_knob_off(K_EFFDET_MERGE_LEVELS);
+  bool merge = B == 1 && eff_split_on(m);
+  merge = merge && !m->knobs.off(K_EFFDET_MERGE_LEVELS);
   if (merge) {      // would the merged pointwise conv run on a conv_split3 kernel without split-K?
     ConvParams q; std::memset(&q, 0, sizeof(q));
     q.B = 1; q.H = Mtot / 256; q.W = 256; q.in_Ha = q.H; q.in_Wa = 256; q.Cin = LF; q.in_ldc = LF; q.Ho = q.H; q.Wo = 256; q.Cout = F;
@@ -289,11 +290,12 @@ int build_effdet_heads(odt_model* m, const Tensor* red, const int* red_ch) {
         }
         op.dw.in = op.dw.lin[0]; op.dw.out = op.dw.lout[0];
         op.dw.H = op.dw.Ho = fh[3]; op.dw.W = op.dw.Wo = fw[3];
+        if (dwconv_plan(op.dw, false, m->knobs)) return 1;
         m->ops.push_back(op);
       }
       const float *wt, *bias;
       if (eff_upload_pw(m, scope, "", true, F, LF, cout, &wt, &bias, "pointwise_kernel")) return 1;
-      const int lco = r32(cout);
+      const int lco = r32(m, cout);
       if (add_conv(m, scope, t1, LF, wt, bias, 1, 1, cout, 1, 1, 0, 0, Mtot / 256, 256, 0, 0, nullptr, 0, false, lco, out, "")) return 1;
       ConvParams& cp = m->convs.back().p;
       cp.relu = act;
@@ -445,13 +447,13 @@ int build_plan_effnet(odt_model* m) {
   }
   Tensor x{};
   if (add_conv(m, "stem", m->image_pad, 32, wt, bias, 3, 1, stemC, 2, 1, 0, 0, Ho, Wo, 0, 0, nullptr, 0, false,
-               r32(stemC), &x, "stem")) return 1;
+               r32(m, stemC), &x, "stem")) return 1;
   m->convs.back().p.relu = 2;
   // ---- MBConv blocks
   Tensor red_feats[6]; int red_ch[6] = {0, 0, 0, 0, 0, 0};
   for (const EffBlock& b : blocks) {
     const std::string p = name + "/blocks_" + std::to_string(b.idx) + "/";
-    const int mid = b.cin * b.expand, lmid = r32(mid);
+    const int mid = b.cin * b.expand, lmid = r32(m, mid);
     int nconv = 0, nbn = 0;
     auto cname = [&]() { const std::string n = nconv == 0 ? "conv2d" : "conv2d_" + std::to_string(nconv); ++nconv; return p + n; };
     auto bname = [&]() { const std::string n = nbn == 0 ? "tpu_batch_normalization" : "tpu_batch_normalization_" + std::to_string(nbn); ++nbn; return p + n; };
@@ -459,9 +461,9 @@ int build_plan_effnet(odt_model* m) {
     Tensor t1 = x;
     int ho, wo, dpt, dpl;
     same(x.h, b.kernel, b.stride, &ho, &dpt); same(x.w, b.kernel, b.stride, &wo, &dpl);
-    const int fmode = eff_fuse_mb_mode();
-    const bool fuse_mb = b.expand != 1 && eff_split_on() && x.C % 32 == 0 && lmid % 64 == 0 && x.h == x.H && x.w == x.W &&
-                         (fmode >= 2 || (fmode == 1 && std::min(ho, wo) >= eff_fuse_mb_min()));
+    const int fmode = eff_fuse_mb_mode(m);
+    const bool fuse_mb = b.expand != 1 && eff_split_on(m) && x.C % 32 == 0 && lmid % 64 == 0 && x.h == x.H && x.w == x.W &&
+                         (fmode >= 2 || (fmode == 1 && std::min(ho, wo) >= eff_fuse_mb_min(m)));
     const float *ewt = nullptr, *ebias = nullptr;
     if (b.expand != 1) {
       const std::string cn = cname(), bn = bname();
@@ -518,10 +520,9 @@ int build_plan_effnet(odt_model* m) {
         op.dw.B = B; op.dw.H = t1.h; op.dw.W = t1.w; op.dw.Ho = ho; op.dw.Wo = wo; op.dw.ldc = lmid;
         op.dw.k = b.kernel; op.dw.stride = b.stride; op.dw.pad_t = dpt; op.dw.pad_l = dpl; op.dw.act = 2;
         // fused squeeze: the depthwise kernel also delivers per-workgroup sums of its output
-        // (sized by the split count the launcher will use: a placeholder makes dwconv_splits() take the fused-squeeze path)
-        op.dw.sum_part = reinterpret_cast<float*>(sizeof(float));
-        se_nsplit = dwconv_splits(op.dw);
-        ODT_CHECK(se_nsplit >= 1 && se_nsplit <= 1024, "dwconv_splits: bad number of partial sums");
+        if (dwconv_plan(op.dw, true, m->knobs)) return 1;
+        se_nsplit = op.dw.nsplit;
+        ODT_CHECK(se_nsplit >= 1 && se_nsplit <= 1024, "dwconv_plan: bad number of partial sums");
         se_part = m->alloc_f((size_t)B * se_nsplit * lmid, false);
         ODT_CHECK(se_part, "device allocation failed (SE)");
         op.dw.sum_part = se_part;
@@ -555,7 +556,7 @@ int build_plan_effnet(odt_model* m) {
       if (upload_raw(m, w1, &op.se.w1) || upload_raw(m, B1->data, &op.se.b1) || upload_raw(m, w2t, &op.se.w2t) ||
           upload_raw(m, B2->data, &op.se.b2)) return 1;
       m->ops.push_back(op);
-      if (B != 1 || !eff_wscale_on()) { Op sc; sc.kind = OP_CSCALE; sc.in = t2; sc.aux = gate; m->ops.push_back(sc); }
+      if (B != 1 || !eff_wscale_on(m)) { Op sc; sc.kind = OP_CSCALE; sc.in = t2; sc.aux = gate; m->ops.push_back(sc); }
     }
     // projection + BN (+ identity skip)
     {
@@ -565,7 +566,7 @@ int build_plan_effnet(odt_model* m) {
       Tensor y{};
       std::string tap = "block_" + std::to_string(b.idx);
       const float* wt_run = wt;
-      if (B == 1 && eff_wscale_on()) {       // the conv runs on gate-scaled weights, rebuilt per forward right behind the gate
+      if (B == 1 && eff_wscale_on(m)) {       // the conv runs on gate-scaled weights, rebuilt per forward right behind the gate
         float* ws = m->alloc_f((size_t)b.cout * lmid, true);
         ODT_CHECK(ws, "device allocation failed (SE)");
         Op wsop; wsop.kind = OP_WSCALE; wsop.conv = (int)m->convs.size(); wsop.wt0 = wt; wsop.aux = gate;
@@ -573,7 +574,7 @@ int build_plan_effnet(odt_model* m) {
         wt_run = ws;
       }
       if (add_conv(m, cn, t2, lmid, wt_run, bias, 1, 1, b.cout, 1, 1, 0, 0, ho, wo, 0, 0, skip ? &inp : nullptr, 1, false,
-                   r32(b.cout), &y, tap)) return 1;
+                   r32(m, b.cout), &y, tap)) return 1;
       if (b.reduction) { m->taps["reduction_" + std::to_string(b.reduction)] = y; red_feats[b.reduction] = y; red_ch[b.reduction] = b.cout; }
       x = y;
     }
@@ -581,7 +582,7 @@ int build_plan_effnet(odt_model* m) {
   if (cfg.eff_det >= 0 && build_effdet_heads(m, red_feats, red_ch)) return 1;
   // the EfficientNet / BiFPN 1x1 convs: bf16x3 split kernels where their tiles (with split-K) fill the chip, as for the
   // FPN detector (conv_arith / ODT_CONV_* apply; ODT_EFFDET_SPLIT=0: exact-f32 MFMA everywhere and 32-channel strides)
-  if (eff_split_on() && attach_split_weights(m)) return 1;
+  if (eff_split_on(m) && attach_split_weights(m)) return 1;
   if (plan_arena(m)) return 1;
   if (upload_conv_records(m)) return 1;
   return 0;

@@ -42,7 +42,7 @@ static int run_ops(odt_model* m, const void* src, int dtype, hipStream_t st, siz
         if (m->profile) ODT_HIP(hipEventRecord(m->ev[2 * op.conv], st));
         for (int k = 0; k < m->conv_nrec[op.conv]; ++k) {
           const int r = m->conv_rec0[op.conv] + k;
-          if (launch_conv(m->conv_recs[r], st, m->convs_dev + r)) { g_err = c.name + ": " + g_err; return 1; }
+          if (launch_conv(m->conv_recs[r], m->convs_dev + r, st)) { g_err = c.name + ": " + g_err; return 1; }
         }
         if (m->profile) ODT_HIP(hipEventRecord(m->ev[2 * op.conv + 1], st));
         break;
@@ -233,7 +233,7 @@ int run_plan(odt_model* m, const void* frames, int dtype, int on_device, hipStre
   }
   // ---- tail overlap (own stream only: a caller's stream must see the whole forward in stream order)
   if (m->tail_overlap < 0) {
-    m->tail_overlap = (cfg.graph != ODT_GRAPH_EFFNET && !m->knob_tail_overlap_off && cfg.tail_overlap >= 0) ? 1 : 0;
+    m->tail_overlap = (cfg.graph != ODT_GRAPH_EFFNET && !m->knobs.off(K_TAIL_OVERLAP) && cfg.tail_overlap >= 0) ? 1 : 0;
     find_overlap_points(m);
     if (m->op_tail == 0) m->tail_overlap = 0;
   }
@@ -241,7 +241,7 @@ int run_plan(odt_model* m, const void* frames, int dtype, int on_device, hipStre
   ++m->forwards_enqueued;
   if (m->tail_overlap == 1 && st == m->own_stream) {
     if (!m->tail_stream) {
-      if (create_side_stream(&m->tail_stream)) return 1;
+      if (create_side_stream(&m->tail_stream, m->knobs)) return 1;
       ODT_HIP(hipEventCreateWithFlags(&m->trunk_done, hipEventDisableTiming));
       ODT_HIP(hipEventCreateWithFlags(&m->tail_done, hipEventDisableTiming));
     }
@@ -298,10 +298,8 @@ int odt_create(const odt_config* cfg, int device, odt_handle* out) {
   ODT_HIP(hipGetDeviceCount(&n));
   ODT_CHECK(device >= 0 && device < n, "odt_create: no such device");
   ODT_HIP(hipSetDevice(device));
-  knobs_reload();
   std::unique_ptr<odt_model> m(new odt_model());
-  m->env_active = knobs_active();
-  m->knob_tail_overlap_off = env_knob_off(K_TAIL_OVERLAP);
+  m->knobs = knobs_read();
   m->cfg = *cfg;
   m->device = device;
   // (non-blocking, round 6: a blocking stream orders itself against every null-stream operation of the process -- another
@@ -351,9 +349,7 @@ int odt_finalize_weights(odt_handle h) {
   ODT_CHECK(h != nullptr, "null handle");
   ODT_CHECK(!h->finalized, "weights already finalized");
   ODT_HIP(hipSetDevice(h->device));
-  knobs_reload();          // the plan is built under the environment of THIS call (tests flip A/B knobs between handles)
-  h->env_active = knobs_active();
-  h->knob_tail_overlap_off = env_knob_off(K_TAIL_OVERLAP);
+  h->knobs = knobs_read();      // the plan is built under the environment of THIS call (tests flip A/B knobs between handles)
   if (build_plan(h)) return 1;
   h->conv_fused.resize(h->convs.size(), 0);
   ODT_HIP(hipDeviceSynchronize());
@@ -443,8 +439,8 @@ int odt_read_outputs(odt_handle h, odt_outputs* out) {
 static int slot_prepare(odt_handle h, odt_model::Slot& sl, size_t in_bytes) {
   const odt_config& cfg = h->cfg;
   const size_t B = cfg.batch, per = cfg.result_per_im, FC = cfg.fpn_channels;
-  if (!h->copy_in && create_side_stream(&h->copy_in)) return 1;
-  if (!h->copy_out && create_side_stream(&h->copy_out)) return 1;
+  if (!h->copy_in && create_side_stream(&h->copy_in, h->knobs)) return 1;
+  if (!h->copy_out && create_side_stream(&h->copy_out, h->knobs)) return 1;
   if (sl.pin_in_bytes < in_bytes) {
     if (sl.pin_in) ODT_HIP(hipHostFree(sl.pin_in));
     if (sl.dev_in) ODT_HIP(hipFree(sl.dev_in));
@@ -673,9 +669,10 @@ int odt_describe(odt_handle h, char* buf, int cap) {
   dev_bytes += h->frames_src.bytes;
   for (const auto& sl : h->slot) dev_bytes += sl.dev_in_bytes;
   // every ODT_* override that was set when the plan was built, by name (knobs.hpp: nothing else reads the environment)
+  const std::vector<std::string> active = h->knobs.active();
   std::string envs;
-  for (size_t i = 0; i < h->env_active.size(); ++i) {
-    std::string e = h->env_active[i];
+  for (size_t i = 0; i < active.size(); ++i) {
+    std::string e = active[i];
     for (char& ch : e) if (ch == '"' || ch == '\\' || (unsigned char)ch < 0x20) ch = '?';
     envs += (i ? ", \"" : "\"") + e + "\"";
   }
@@ -690,7 +687,7 @@ int odt_describe(odt_handle h, char* buf, int cap) {
                 h->policy.arith != 0 && fam[2] > 0 ? "f32 through fp16x2 / bf16x3 split products"
                     : (h->policy.arith != 0 && fam[1] + fam[3] > 0 ? "f32 through bf16x3 split products" : "exact f32 MFMA"),
                 (int)h->convs.size() - nfused, nfused, fam[0], fam[1] + fam[3], fam[2], h->convs_h2f, h->stem_fused, h->mb_fused, fam[3], fam[1], fam[2], nsk, h->policy.family,
-                h->policy.min_tiles, h->policy.min_tiles3, h->policy.min_k, (int)h->env_active.size(), envs.c_str(),
+                h->policy.min_tiles, h->policy.min_tiles3, h->policy.min_k, (int)active.size(), envs.c_str(),
                 dev_bytes, h->arena_bytes[0], h->arena_bytes[1], h->vt.size(), h->virtual_tensor_bytes,
                 h->dedicated_tensor_bytes, h->cfg.keep_taps, h->chunked_convs);
   ODT_CHECK((int)std::strlen(tmp) < cap, "odt_describe: buffer too small");

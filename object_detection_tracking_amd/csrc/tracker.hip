@@ -195,9 +195,8 @@ int CosineCtx::run(int dev, const float* const* gal_rows, int G, const int* seg,
     // assignment: 6 ms of "tracking" per frame instead of 0.5).  Streams of another priority get queues of their own.
     int prio_least = 0, prio_greatest = 0;
     ODT_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    knobs_reload();
-    const bool flat = env_knob_off(K_COSINE_STREAM_PRIORITY);   // A/B knob
-    if (env_knob(K_COSINE_STREAM_PRIORITY).set && env_knob(K_COSINE_STREAM_PRIORITY).i < 0)      // A/B: the LOWEST priority (its own queues too)
+    const bool flat = knobs.off(K_COSINE_STREAM_PRIORITY);   // A/B knob
+    if (knobs.get(K_COSINE_STREAM_PRIORITY).set && knobs.get(K_COSINE_STREAM_PRIORITY).i < 0)      // A/B: the LOWEST priority (its own queues too)
       ODT_HIP(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, prio_least));
     else if (flat) ODT_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     else ODT_HIP(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, prio_greatest));
@@ -231,7 +230,7 @@ int CosineCtx::run(int dev, const float* const* gal_rows, int G, const int* seg,
     ODT_HIP(hipMalloc((void**)&d_cost, want * 8));
     cap_cost = want;
   }
-  static const bool timing = env_knob(K_TRACKER_TIMING).set;      // tuning aid: where a call's wall time goes
+  const bool timing = knobs.get(K_TRACKER_TIMING).set;      // tuning aid: where a call's wall time goes
   static double acc_t[5] = {0, 0, 0, 0, 0}; static long acc_n = 0;
   auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double c0 = timing ? now() : 0.0;

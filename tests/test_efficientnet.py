@@ -1,4 +1,6 @@
 """EfficientDet path, backbone (detector half -- in progress)."""
+import os
+
 import numpy as np
 import pytest
 
@@ -97,6 +99,42 @@ def test_backbone_mbconv_expand_dw_in_one_kernel(backend, monkeypatch):
   if name == "hip":
     monkeypatch.setenv("ODT_EFFDET_FUSE_MB", "2")
     _backbone_parity(lib, "efficientnet-b6", 384, 512)
+
+
+def test_handle_keeps_the_knobs_of_its_plan(emu_lib, monkeypatch):
+  """A handle launches what its plan recorded under the ODT_* overrides of its own odt_finalize_weights (csrc/knobs.hpp):
+  creating another handle under another environment changes neither its kernel choices (the exact-f32 tile, the
+  depthwise outputs per thread) nor the depthwise split count its fused-squeeze scratch was sized for -- a launch-time
+  recount from the new environment (no ODT_DW_SUMCAP: more splits) wrote past that scratch.  Simulator only: a regression
+  here is an out-of-bounds write."""
+  from object_detection_tracking_amd.efficientdet import EfficientNetBackbone, synthetic_backbone_weights
+  from object_detection_tracking_amd.weights import synthetic_frames
+  for k in list(os.environ):
+    if k.startswith("ODT_"):
+      monkeypatch.delenv(k)
+  w = synthetic_backbone_weights("efficientnet-b0", 0)
+  fr = synthetic_frames(1, 70, 100, seed=5)
+  env_a = {"ODT_EFFDET_FUSE_MB": "0", "ODT_DW_SUMCAP": "1", "ODT_DW_PX": "4", "ODT_CONV_TILE": "1"}
+  for k, v in env_a.items():
+    monkeypatch.setenv(k, v)
+  a = EfficientNetBackbone("efficientnet-b0", w, 1, 70, 100, lib=emu_lib)
+  b = None
+  try:
+    assert a.describe()["exact_f32_mfma_launches"] > 0
+    before = a.features(fr)
+    monkeypatch.delenv("ODT_DW_SUMCAP")
+    monkeypatch.delenv("ODT_DW_PX")
+    monkeypatch.setenv("ODT_CONV_TILE", "3")
+    b = EfficientNetBackbone("efficientnet-b0", w, 1, 70, 100, lib=emu_lib)
+    after = a.features(fr)
+    for lvl in before:
+      assert np.array_equal(before[lvl], after[lvl]), lvl
+    assert sorted(a.describe()["env_overrides"]) == sorted("%s=%s" % kv for kv in env_a.items())
+    assert sorted(b.describe()["env_overrides"]) == ["ODT_CONV_TILE=3", "ODT_EFFDET_FUSE_MB=0"]
+  finally:
+    a.close()
+    if b is not None:
+      b.close()
 
 
 @pytest.mark.gpu
