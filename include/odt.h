@@ -387,6 +387,54 @@ int odt_op_class_nms(int device, int graph, int B, int N, int C, const float* bo
                      float nms_thresh, int per_im, float* boxes, float* scores,
                      int32_t* labels, int32_t* valid);
 
+/* ---- EfficientDet kernels alone (host pointers, null stream, the ODT_* knobs as they are at the call).  Every output
+ * and scratch buffer these allocate ends in a guard region of sentinel bytes; a launch that wrote into one fails the call
+ * with an error naming the buffer.  Outputs no kernel wrote read back as 0x7F7F7F7F (3.39e38). ---------------------- */
+
+/* depthwise k x k conv (k = 3 / 5, stride 1 / 2, explicit pads, + bias, act 0 none / 2 swish) through dwconv_plan +
+ * launch_dwconv.  in [B,H,W,ldc] (ldc % 4 == 0), wt [k*k][ldc], bias [ldc], out [B,Ho,Wo,ldc].  nmaps 1..5: the multi-map
+ * launch (B = 1, stride 1, Ho = H, Wo = W per map): map_hw [nmaps][2], in / out the maps' [h,w,ldc] tensors back to back.
+ * w1 != NULL: the fused squeeze -- sum_part [B][nsplit][ldc] as dwconv_plan sized it, then the gate from those parts
+ * (w1 / w2t [se][ldc], b1 [se], b2 [mid]) -> mean [B,ldc], gate [B,ldc] (pad channels 0).  info (optional) [4]: px,
+ * nsplit, xcd_bands, channel quads per workgroup -- what the plan chose. */
+int odt_op_dwconv(int device, const float* in, int B, int H, int W, int ldc, const float* wt, const float* bias, int k,
+                  int stride, int pad_t, int pad_l, int Ho, int Wo, int act, int nmaps, const int32_t* map_hw, int se,
+                  int mid, const float* w1, const float* b1, const float* w2t, const float* b2, float* out, float* mean,
+                  float* gate, int32_t* info);
+/* squeeze-excite gate from the activations (launch_se_gate: channel sum -> fold -> reduce -> expand): x [B,HW,ldc] ->
+ * mean, gate [B,ldc]; scaled != NULL: x * gate per channel (launch_channel_scale) [B,HW,ldc].  info (optional) [1]: the
+ * channel-sum pixel splits. */
+int odt_op_se_gate(int device, const float* x, int B, int HW, int ldc, int mid, int se, const float* w1, const float* b1,
+                   const float* w2t, const float* b2, float* mean, float* gate, float* scaled, int32_t* info);
+/* BiFPN node input fusion (launch_bifpn_fuse): n = 1..3 inputs ins[k] [B,in_hw[k][0],in_hw[k][1],ldc], mode[k] 0 same
+ * size, 1 nearest resize, 2 3x3 / s2 'SAME' max pool with pads[k] = (top, left); wsm != NULL: 'fastattn' with the raw
+ * WSM scalars [n], else a plain sum; act 0 / 2 (swish).  out [B,h,w,ldc]. */
+int odt_op_bifpn_fuse(int device, int n, const float* const* ins, const int32_t* in_hw, const int32_t* mode,
+                      const int32_t* pads, const float* wsm, int act, int B, int h, int w, int ldc, float* out);
+/* the fused MBConv front half (launch_mbconv_expand_dw): x [B,H,W,in_ldc] (in_ldc % 32 == 0), expand weights e_wt
+ * [mid][in_ldc] as the plan's bf16x3 piece image, e_bias [mid], dw_wt [k*k][lmid], dw_bias [lmid] (lmid % 64 == 0) ->
+ * out [B,Ho,Wo,lmid]; w1 != NULL: the squeeze partial sums and the gate from them as in odt_op_dwconv.  info (optional)
+ * [1]: nsplit. */
+int odt_op_mbconv_expand_dw(int device, const float* x, int B, int H, int W, int in_ldc, const float* e_wt,
+                            const float* e_bias, int mid, int lmid, const float* dw_wt, const float* dw_bias, int k,
+                            int stride, int pad_t, int pad_l, int Ho, int Wo, int se, const float* w1, const float* b1,
+                            const float* w2t, const float* b2, float* out, float* mean, float* gate, int32_t* info);
+/* the EfficientDet detection tail (launch_effdet_post): per level l = 0..4 cls[l] [B,npix[l],ldc_cls] (9 * ncls valid,
+ * anchor-major), box[l] [B,npix[l],ldc_box] (36 valid), anchors [sum 9 npix, 4].  Candidates after sort + decode:
+ * cand_idx [B,k] (optional: the selected anchor * ncls + class indices, sorted on the host by their keys -- the set the
+ * selection chose in reference order; the device sort's own order shows in the other cand_* arrays), cand_boxes [B,k,4] y1x1y2x2, cand_scores, cand_cls, cand_lvl [B,k]
+ * (each optional); outputs boxes [B,max_out,4] x1y1x2y2 * image_scale, scores, labels (1-based), levels [B,max_out],
+ * valid [B].  A top-k slot the selection left unfilled is an error of the call. */
+int odt_op_effdet_post(int device, int B, int ncls, const int32_t* npix, int ldc_cls, int ldc_box,
+                       const float* const* cls, const float* const* box, const float* anchors, int k, int max_out,
+                       float score_thresh, float iou_thresh, float image_scale, int32_t* cand_idx, float* cand_boxes,
+                       float* cand_scores, int32_t* cand_cls, int32_t* cand_lvl, float* boxes, float* scores,
+                       int32_t* labels, int32_t* levels, int32_t* valid);
+/* the EfficientDet preprocess (BGR -> normalised RGB, HWC4, zero padded to [B,Hp,Wp,4]) of frames [B,Hs,Ws,3] (u8 or
+ * f32); resize = 1: bilinear TF-1.x resize to [Hr,Wr] first (launch_preprocess_rgb_resize), 0: launch_preprocess_rgb. */
+int odt_op_preprocess_rgb(int device, const void* frames, int dtype, int B, int Hs, int Ws, int Hr, int Wr, int pad_t,
+                          int pad_l, int Hp, int Wp, int resize, float* out);
+
 #ifdef __cplusplus
 }
 #endif

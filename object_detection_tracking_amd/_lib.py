@@ -82,7 +82,9 @@ class OdtLib(object):
       "odt_profile_read", "odt_profile_layer", "odt_probe_mfma_bf16", "odt_nn_cosine", "odt_op_conv2d", "odt_op_conv2d_cat",
       "odt_op_bottleneck_tail", "odt_op_stem", "odt_op_preprocess",
       "odt_op_maxpool", "odt_op_topk", "odt_op_nms", "odt_op_proposals",
-      "odt_op_roi_align", "odt_op_detections", "odt_op_class_nms", "odt_tracker_create", "odt_tracker_destroy",
+      "odt_op_roi_align", "odt_op_detections", "odt_op_class_nms",
+      "odt_op_dwconv", "odt_op_se_gate", "odt_op_bifpn_fuse", "odt_op_mbconv_expand_dw", "odt_op_effdet_post",
+      "odt_op_preprocess_rgb", "odt_tracker_create", "odt_tracker_destroy",
       "odt_tracker_predict", "odt_tracker_update", "odt_tracker_tracks", "odt_lsap", "odt_tracker_nms",
       "odt_tmot_create", "odt_tmot_destroy", "odt_tmot_reset", "odt_tmot_update", "odt_tmot_tracks",
   ]
@@ -167,6 +169,18 @@ class OdtLib(object):
                                                     c_float_p, c_int_p, c_int_p]
     d.odt_op_class_nms.argtypes = [C.c_int] * 5 + [c_float_p, c_float_p, c_int_p, C.c_float, C.c_float, C.c_int,
                                                    c_float_p, c_float_p, c_int_p, c_int_p]
+
+    d.odt_op_dwconv.argtypes = [C.c_int, c_float_p] + [C.c_int] * 4 + [c_float_p, c_float_p] + [C.c_int] * 8 + \
+        [c_int_p, C.c_int, C.c_int] + [c_float_p] * 7 + [c_int_p]
+    d.odt_op_se_gate.argtypes = [C.c_int, c_float_p] + [C.c_int] * 5 + [c_float_p] * 7 + [c_int_p]
+    d.odt_op_bifpn_fuse.argtypes = [C.c_int, C.c_int, C.POINTER(c_float_p), c_int_p, c_int_p, c_int_p, c_float_p] + \
+        [C.c_int] * 5 + [c_float_p]
+    d.odt_op_mbconv_expand_dw.argtypes = [C.c_int, c_float_p] + [C.c_int] * 4 + [c_float_p] * 2 + [C.c_int] * 2 + \
+        [c_float_p] * 2 + [C.c_int] * 7 + [c_float_p] * 7 + [c_int_p]
+    d.odt_op_effdet_post.argtypes = [C.c_int] * 3 + [c_int_p, C.c_int, C.c_int, C.POINTER(c_float_p), C.POINTER(c_float_p),
+                                     c_float_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, c_int_p, c_float_p,
+                                     c_float_p, c_int_p, c_int_p, c_float_p, c_float_p, c_int_p, c_int_p, c_int_p]
+    d.odt_op_preprocess_rgb.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 11 + [c_float_p]
 
   def check(self, rc):
     if rc != 0:

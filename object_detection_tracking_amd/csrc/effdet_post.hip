@@ -120,6 +120,15 @@ __global__ void __launch_bounds__(1024) eff_sort_decode_kernel(EffPostParams p, 
   for (int i = tid; i < k; i += nthr) {
     const unsigned long long key = s[i];
     const unsigned e = key64_index(key);
+    if (e >= (unsigned)p.anchor_off[5] * (unsigned)p.ncls) {
+      // a slot the compaction never filled (no valid key carries this index): flag it and read nothing through it
+      float* o = p.cand_boxes + ((size_t)b * p.k + i) * 4;
+      o[0] = o[1] = o[2] = o[3] = 0.f;
+      p.cand_scores[(size_t)b * p.k + i] = 0.f;
+      p.cand_cls[(size_t)b * p.k + i] = -1;
+      p.cand_lvl[(size_t)b * p.k + i] = -1;
+      continue;
+    }
     const float logit = key_to_float((unsigned)(key >> 32));
     const unsigned a = e / (unsigned)p.ncls, cls = e - a * (unsigned)p.ncls;
     int l = 0;

@@ -465,10 +465,10 @@ int launch_channel_mean(const float* in, int B, int HW, int ldc, float* scratch,
 // channel_sum_kernel partials (scratch) + the gate, replacing channel_mean_final + two tiny GEMMs
 int launch_se_gate(const float* in, const SeGateParams& p0, int B, float* scratch, hipStream_t stream) {
   SeGateParams p = p0;
+  ODT_CHECK(p.ldc <= kSeMaxC && p.se <= kSeMaxR, "se_gate: channel count too large for the LDS staging");
   p.nsplit = channel_mean_splits(p.HW, p.ldc, B); p.part = scratch;
   hipLaunchKernelGGL(channel_sum_kernel, dim3((p.ldc + 63) / 64, B, p.nsplit), dim3(256), 0, stream, in, p.HW, p.ldc,
                      p.nsplit, scratch);
-  ODT_CHECK(p.ldc <= kSeMaxC && p.se <= kSeMaxR, "se_gate: channel count too large for the LDS staging");
   hipLaunchKernelGGL(channel_mean_fold_kernel, dim3((p.ldc + 63) / 64, B), dim3(256), 0, stream, p);
   hipLaunchKernelGGL(se_reduce_kernel, dim3((p.se + 3) / 4, B), dim3(256), 0, stream, p);
   hipLaunchKernelGGL(se_expand_kernel, dim3((p.mid + 255) / 256, B), dim3(256), 0, stream, p);

@@ -305,7 +305,7 @@ struct EffPostParams {
   float score_thresh, iou_thresh, image_scale;
   unsigned* keys;          // scratch [total * ncls]
   unsigned* hist;          // scratch [256]
-  unsigned* state;         // scratch [4]
+  unsigned* state;         // scratch [5]
   unsigned long long* sel; // scratch [B, k]
   float* cand_boxes; float* cand_scores; int* cand_cls; int* cand_lvl;   // [B, k(,4)]
   float* out_boxes; float* out_scores; int* out_labels; int* out_levels; int* out_valid;   // [B, max_out(,4)], [B]

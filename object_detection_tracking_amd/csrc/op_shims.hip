@@ -1,5 +1,7 @@
 // Stand-alone op entry points of the C ABI (include/odt.h: odt_op_*, odt_nn_cosine): host pointers in and out, each
 // runs exactly the kernels the forward uses -- what the staged parity tests call.
+#include <functional>
+
 #include "odt_model.hpp"
 
 using namespace odt;
@@ -68,6 +70,74 @@ int run_conv(ConvParams q, const Knobs& kn) {
   ODT_HIP(hipMalloc((void**)&tmp.rec, sizeof(ConvParams)));
   ODT_HIP(hipMemcpy(tmp.rec, &q, sizeof(ConvParams), hipMemcpyHostToDevice));
   return launch_conv(q, tmp.rec, nullptr);
+}
+
+// device buffers of the EfficientDet op shims (odt_op_dwconv ... odt_op_preprocess_rgb): every one ends in kGuardBytes of
+// sentinel bytes, and GBufs::check() reports -- by the buffer's name -- a launch that wrote into them.  There is no
+// sanitizer on the device: this turns a write past the end of an output or scratch buffer into an error of the call.
+// Outputs start as sentinel bytes too (an element no kernel wrote reads back as 0x7F7F7F7F, 3.39e38), except where the
+// plan zero-initialises the buffer and relies on that (the squeeze-excite gate).
+constexpr size_t kGuardBytes = 1024;
+constexpr int kGuardByte = 0x7F;
+
+struct GBuf {
+  unsigned char* d = nullptr;
+  size_t bytes = 0;
+  std::string name;
+  ~GBuf() { if (d) (void)hipFree(d); }
+};
+
+struct GBufs {
+  std::vector<std::unique_ptr<GBuf>> v;
+  // nbytes payload bytes, payload filled with `fill` (a byte value) or the sentinel (fill < 0), then the guard
+  template <typename T>
+  int alloc(const char* name, size_t count, T** out, int fill = -1, const void* host = nullptr) {
+    v.emplace_back(new GBuf());
+    GBuf& g = *v.back();
+    g.name = name; g.bytes = count * sizeof(T);
+    ODT_HIP(hipMalloc((void**)&g.d, g.bytes + kGuardBytes));
+    if (host != nullptr) { ODT_HIP(hipMemcpy(g.d, host, g.bytes, hipMemcpyHostToDevice)); }
+    else { ODT_HIP(hipMemset(g.d, fill < 0 ? kGuardByte : fill, g.bytes)); }
+    ODT_HIP(hipMemset(g.d + g.bytes, kGuardByte, kGuardBytes));
+    *out = reinterpret_cast<T*>(g.d);
+    return 0;
+  }
+  // after the launches: synchronise, then every guard region must still hold the sentinel
+  int check(const char* op) {
+    ODT_HIP(hipDeviceSynchronize());
+    std::vector<unsigned char> h(kGuardBytes);
+    for (const auto& g : v) {
+      ODT_HIP(hipMemcpy(h.data(), g->d + g->bytes, kGuardBytes, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < kGuardBytes; ++i)
+        ODT_CHECK(h[i] == (unsigned char)kGuardByte, std::string(op) + ": write past the end of " + g->name + " (guard byte " +
+                                                         std::to_string(i) + ")");
+    }
+    return 0;
+  }
+};
+
+template <typename T>
+int get_dev(T* host, const T* dev, size_t count) {
+  if (host != nullptr && count > 0) ODT_HIP(hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// the squeeze-excite gate from per-split partial sums as the plan runs it (OP_SE_GATE_MEAN with a fused squeeze):
+// fold + reduce + expand; mean / r scratch start as sentinels, the gate as zeros (pad channels stay 0)
+int se_from_parts(GBufs& g, const float* part, int nsplit, int B, int HW, int ldc, int mid, int se, const float* w1,
+                  const float* b1, const float* w2t, const float* b2, float** mean, float** gate) {
+  ODT_CHECK(w1 && b1 && w2t && b2 && mid >= 1 && mid <= ldc && se >= 1, "squeeze-excite: bad weights / sizes");
+  SeGateParams sp; std::memset(&sp, 0, sizeof(sp));
+  float *dw1, *db1, *dw2t, *db2;
+  if (g.alloc("se_w1", (size_t)se * ldc, &dw1, -1, w1) || g.alloc("se_b1", (size_t)se, &db1, -1, b1) ||
+      g.alloc("se_w2t", (size_t)se * ldc, &dw2t, -1, w2t) || g.alloc("se_b2", (size_t)mid, &db2, -1, b2) ||
+      g.alloc("se_mean", (size_t)B * ldc, &sp.mean) || g.alloc("se_r", (size_t)B * 256, &sp.r) ||
+      g.alloc("se_gate", (size_t)B * ldc, &sp.gate, 0)) return 1;
+  sp.part = part; sp.nsplit = nsplit; sp.HW = HW; sp.ldc = ldc; sp.mid = mid; sp.se = se;
+  sp.w1 = dw1; sp.b1 = db1; sp.w2t = dw2t; sp.b2 = db2;
+  if (launch_se_gate_from_parts(sp, B, nullptr)) return 1;
+  *mean = sp.mean; *gate = sp.gate;
+  return 0;
 }
 
 }  // namespace
@@ -493,6 +563,227 @@ int odt_op_class_nms(int device, int graph, int B, int N, int C, const float* bo
   ODT_HIP(hipDeviceSynchronize());
   if (ob.get(boxes, ob.n) || op.get(scores, op.n) || ol.get(labels, ol.n)) return 1;
   return ov.get(valid, B);
+}
+
+int odt_op_dwconv(int device, const float* in, int B, int H, int W, int ldc, const float* wt, const float* bias, int k,
+                  int stride, int pad_t, int pad_l, int Ho, int Wo, int act, int nmaps, const int32_t* map_hw, int se,
+                  int mid, const float* w1, const float* b1, const float* w2t, const float* b2, float* out, float* mean,
+                  float* gate, int32_t* info) {
+  ODT_CHECK(in && wt && bias && out, "odt_op_dwconv: null argument");
+  ODT_CHECK(ldc > 0 && ldc % 4 == 0 && B >= 1 && nmaps >= 0 && nmaps <= 5 && (act == 0 || act == 2), "odt_op_dwconv: bad sizes");
+  ODT_CHECK(nmaps == 0 || (map_hw != nullptr && w1 == nullptr), "odt_op_dwconv: multi-map launches take map sizes and no squeeze");
+  if (set_dev(device)) return 1;
+  DwConvParams p; std::memset(&p, 0, sizeof(p));
+  p.B = B; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.ldc = ldc; p.k = k; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
+  p.act = act; p.nlvl = nmaps;
+  size_t npix_in = (size_t)B * H * W, npix_out = (size_t)B * Ho * Wo;
+  if (nmaps > 0) {
+    npix_in = npix_out = 0;
+    for (int i = 0; i < nmaps; ++i) {
+      ODT_CHECK(map_hw[2 * i] >= 1 && map_hw[2 * i + 1] >= 1, "odt_op_dwconv: empty map");
+      p.lH[i] = map_hw[2 * i]; p.lW[i] = map_hw[2 * i + 1];
+      npix_in += (size_t)p.lH[i] * p.lW[i];
+    }
+    npix_out = npix_in;
+  }
+  const bool squeeze = w1 != nullptr;
+  const Knobs kn = knobs_read();      // (the environment as it is at this call)
+  if (dwconv_plan(p, squeeze, kn)) return 1;
+  GBufs g;
+  float *din, *dout;
+  const float *dwt, *dbias;
+  if (g.alloc("in", npix_in * ldc, &din, -1, in) || g.alloc("wt", (size_t)k * k * ldc, (float**)&dwt, -1, wt) ||
+      g.alloc("bias", (size_t)ldc, (float**)&dbias, -1, bias) || g.alloc("out", npix_out * ldc, &dout)) return 1;
+  p.in = din; p.wt = dwt; p.bias = dbias; p.out = dout;
+  for (size_t i = 0, off = 0; i < (size_t)nmaps; off += (size_t)p.lH[i] * p.lW[i] * ldc, ++i) {
+    p.lin[i] = din + off; p.lout[i] = dout + off;
+  }
+  if (squeeze) {      // sum_part sized from the split count dwconv_plan chose, as the plan sizes it
+    ODT_CHECK(p.nsplit >= 1 && p.nsplit <= 1024, "dwconv_plan: bad number of partial sums");
+    if (g.alloc("sum_part", (size_t)B * p.nsplit * ldc, &p.sum_part)) return 1;
+  }
+  if (launch_dwconv(p, nullptr)) return 1;
+  float *dmean = nullptr, *dgate = nullptr;
+  if (squeeze && se_from_parts(g, p.sum_part, p.nsplit, B, Ho * Wo, ldc, mid, se, w1, b1, w2t, b2, &dmean, &dgate)) return 1;
+  if (g.check("odt_op_dwconv")) return 1;
+  if (info != nullptr) { info[0] = p.px; info[1] = p.nsplit; info[2] = p.xcd_bands; info[3] = p.cqn; }
+  if (get_dev(out, dout, npix_out * ldc)) return 1;
+  if (squeeze && (get_dev(mean, dmean, (size_t)B * ldc) || get_dev(gate, dgate, (size_t)B * ldc))) return 1;
+  return 0;
+}
+
+int odt_op_se_gate(int device, const float* x, int B, int HW, int ldc, int mid, int se, const float* w1, const float* b1,
+                   const float* w2t, const float* b2, float* mean, float* gate, float* scaled, int32_t* info) {
+  ODT_CHECK(x && w1 && b1 && w2t && b2 && mean && gate, "odt_op_se_gate: null argument");
+  ODT_CHECK(B >= 1 && HW >= 1 && ldc > 0 && ldc % 4 == 0 && mid >= 1 && mid <= ldc && se >= 1, "odt_op_se_gate: bad sizes");
+  if (set_dev(device)) return 1;
+  GBufs g;
+  SeGateParams sp; std::memset(&sp, 0, sizeof(sp));
+  float *dx, *dw1, *db1, *dw2t, *db2, *scratch;
+  const int ns = channel_mean_splits(HW, ldc, B);
+  if (g.alloc("x", (size_t)B * HW * ldc, &dx, -1, x) || g.alloc("se_w1", (size_t)se * ldc, &dw1, -1, w1) ||
+      g.alloc("se_b1", (size_t)se, &db1, -1, b1) || g.alloc("se_w2t", (size_t)se * ldc, &dw2t, -1, w2t) ||
+      g.alloc("se_b2", (size_t)mid, &db2, -1, b2) || g.alloc("channel_sum scratch", (size_t)B * ns * ldc, &scratch) ||
+      g.alloc("se_mean", (size_t)B * ldc, &sp.mean) || g.alloc("se_r", (size_t)B * 256, &sp.r) ||
+      g.alloc("se_gate", (size_t)B * ldc, &sp.gate, 0)) return 1;
+  sp.HW = HW; sp.ldc = ldc; sp.mid = mid; sp.se = se; sp.w1 = dw1; sp.b1 = db1; sp.w2t = dw2t; sp.b2 = db2;
+  if (launch_se_gate(dx, sp, B, scratch, nullptr)) return 1;
+  if (scaled != nullptr && launch_channel_scale(dx, sp.gate, B, HW, ldc, nullptr)) return 1;
+  if (g.check("odt_op_se_gate")) return 1;
+  if (info != nullptr) info[0] = ns;
+  if (get_dev(mean, sp.mean, (size_t)B * ldc) || get_dev(gate, sp.gate, (size_t)B * ldc)) return 1;
+  return get_dev(scaled, dx, (size_t)B * HW * ldc);
+}
+
+int odt_op_bifpn_fuse(int device, int n, const float* const* ins, const int32_t* in_hw, const int32_t* mode,
+                      const int32_t* pads, const float* wsm, int act, int B, int h, int w, int ldc, float* out) {
+  ODT_CHECK(ins && in_hw && mode && out, "odt_op_bifpn_fuse: null argument");
+  ODT_CHECK(n >= 1 && n <= 3 && B >= 1 && h >= 1 && w >= 1 && ldc > 0 && ldc % 4 == 0 && (act == 0 || act == 2),
+            "odt_op_bifpn_fuse: bad sizes");
+  if (set_dev(device)) return 1;
+  FuseParams p; std::memset(&p, 0, sizeof(p));
+  GBufs g;
+  static const char* names[3] = {"in0", "in1", "in2"};
+  for (int k = 0; k < n; ++k) {
+    const int ih = in_hw[2 * k], iw = in_hw[2 * k + 1];
+    ODT_CHECK(ins[k] != nullptr && ih >= 1 && iw >= 1, "odt_op_bifpn_fuse: bad input");
+    p.ih[k] = ih; p.iw[k] = iw; p.mode[k] = mode[k]; p.sy[k] = p.sx[k] = 1.f; p.pt[k] = p.pl[k] = 0;
+    // (the plan's fuse_input: same size, nearest up-sampling with in / out ratios, 3x3 / s2 'SAME' max pool)
+    if (mode[k] == 0) {
+      ODT_CHECK(ih == h && iw == w, "odt_op_bifpn_fuse: mode 0 input must have the node's size");
+    } else if (mode[k] == 1) {
+      ODT_CHECK(ih <= h && iw <= w, "odt_op_bifpn_fuse: mode 1 input must not be larger than the node");
+      p.sy[k] = (float)ih / (float)h; p.sx[k] = (float)iw / (float)w;
+    } else {
+      ODT_CHECK(mode[k] == 2 && pads != nullptr && (ih + 1) / 2 == h && (iw + 1) / 2 == w,
+                "odt_op_bifpn_fuse: mode 2 input must be the 3x3 / s2 'SAME' pool of the node's size");
+      p.pt[k] = pads[2 * k]; p.pl[k] = pads[2 * k + 1];
+    }
+    float* d;
+    if (g.alloc(names[k], (size_t)B * ih * iw * ldc, &d, -1, ins[k])) return 1;
+    p.in[k] = d;
+  }
+  if (wsm != nullptr) {      // 'fastattn': relu of the WSM scalars, tf.add_n left to right + 0.0001
+    for (int k = 0; k < n; ++k) p.wgt[k] = std::max(wsm[k], 0.f);
+    float tot = p.wgt[0];
+    for (int k = 1; k < n; ++k) tot = tot + p.wgt[k];
+    p.denom = tot + 0.0001f; p.weighted = 1;
+  }
+  p.n = n; p.act = act; p.B = B; p.h = h; p.w = w; p.ldc = ldc;
+  if (g.alloc("out", (size_t)B * h * w * ldc, &p.out)) return 1;
+  if (launch_bifpn_fuse(p, nullptr)) return 1;
+  if (g.check("odt_op_bifpn_fuse")) return 1;
+  return get_dev(out, p.out, (size_t)B * h * w * ldc);
+}
+
+int odt_op_mbconv_expand_dw(int device, const float* x, int B, int H, int W, int in_ldc, const float* e_wt,
+                            const float* e_bias, int mid, int lmid, const float* dw_wt, const float* dw_bias, int k,
+                            int stride, int pad_t, int pad_l, int Ho, int Wo, int se, const float* w1, const float* b1,
+                            const float* w2t, const float* b2, float* out, float* mean, float* gate, int32_t* info) {
+  ODT_CHECK(x && e_wt && e_bias && dw_wt && dw_bias && out, "odt_op_mbconv_expand_dw: null argument");
+  ODT_CHECK(B >= 1 && H >= 1 && W >= 1 && Ho >= 1 && Wo >= 1 && mid >= 1 && mid <= lmid, "odt_op_mbconv_expand_dw: bad sizes");
+  if (set_dev(device)) return 1;
+  GBufs g;
+  MbExpandDwParams q; std::memset(&q, 0, sizeof(q));
+  float *dx, *dew, *deb, *ddw, *ddb, *img;
+  if (g.alloc("x", (size_t)B * H * W * in_ldc, &dx, -1, x) || g.alloc("e_wt", (size_t)mid * in_ldc, &dew, -1, e_wt) ||
+      g.alloc("e_bias", (size_t)mid, &deb, -1, e_bias) || g.alloc("dw_wt", (size_t)k * k * lmid, &ddw, -1, dw_wt) ||
+      g.alloc("dw_bias", (size_t)lmid, &ddb, -1, dw_bias) ||
+      g.alloc("w_img", (mbconv_expand_weight_bytes(lmid, in_ldc) + 3) / 4, &img) ||
+      g.alloc("out", (size_t)B * Ho * Wo * lmid, &q.out)) return 1;
+  {   // the expand weights as the bf16x3 piece image of the one-stage 256 x 64 kernel (plan_effdet.hip, fused MBConv)
+    ConvParams cp; std::memset(&cp, 0, sizeof(cp));
+    cp.wt = dew; cp.Cout = mid; cp.Cin = in_ldc; cp.kh = 1; cp.kw = 1; cp.wt_split_kind = 1; cp.wt_split_bn = 64;
+    if (conv_make_split_weights(cp, img, nullptr)) return 1;
+  }
+  q.x = dx; q.B = B; q.H = H; q.W = W; q.in_ldc = in_ldc; q.w_img = img; q.e_bias = deb; q.mid = mid; q.lmid = lmid;
+  q.dw_wt = ddw; q.dw_bias = ddb; q.Ho = Ho; q.Wo = Wo; q.k = k; q.stride = stride; q.pad_t = pad_t; q.pad_l = pad_l;
+  q.nsplit = 0;
+  q.nsplit = mbconv_expand_dw_splits(q);
+  const bool squeeze = w1 != nullptr;
+  if (squeeze && g.alloc("sum_part", (size_t)B * q.nsplit * lmid, &q.sum_part)) return 1;
+  if (launch_mbconv_expand_dw(q, nullptr)) return 1;
+  float *dmean = nullptr, *dgate = nullptr;
+  if (squeeze && se_from_parts(g, q.sum_part, q.nsplit, B, Ho * Wo, lmid, mid, se, w1, b1, w2t, b2, &dmean, &dgate)) return 1;
+  if (g.check("odt_op_mbconv_expand_dw")) return 1;
+  if (info != nullptr) info[0] = q.nsplit;
+  if (get_dev(out, q.out, (size_t)B * Ho * Wo * lmid)) return 1;
+  if (squeeze && (get_dev(mean, dmean, (size_t)B * lmid) || get_dev(gate, dgate, (size_t)B * lmid))) return 1;
+  return 0;
+}
+
+int odt_op_effdet_post(int device, int B, int ncls, const int32_t* npix, int ldc_cls, int ldc_box,
+                       const float* const* cls, const float* const* box, const float* anchors, int k, int max_out,
+                       float score_thresh, float iou_thresh, float image_scale, int32_t* cand_idx, float* cand_boxes,
+                       float* cand_scores, int32_t* cand_cls, int32_t* cand_lvl, float* boxes, float* scores,
+                       int32_t* labels, int32_t* levels, int32_t* valid) {
+  ODT_CHECK(npix && cls && box && anchors && boxes && scores && labels && levels && valid, "odt_op_effdet_post: null argument");
+  ODT_CHECK(B >= 1 && ncls >= 1 && ldc_cls >= 9 * ncls && ldc_box >= 36, "odt_op_effdet_post: bad sizes");
+  if (set_dev(device)) return 1;
+  EffPostParams p; std::memset(&p, 0, sizeof(p));
+  GBufs g;
+  static const char* cn[5] = {"cls3", "cls4", "cls5", "cls6", "cls7"};
+  static const char* bn[5] = {"box3", "box4", "box5", "box6", "box7"};
+  int tot = 0;
+  for (int l = 0; l < 5; ++l) {
+    ODT_CHECK(npix[l] >= 1 && cls[l] && box[l], "odt_op_effdet_post: bad level");
+    float *dc, *db;
+    if (g.alloc(cn[l], (size_t)B * npix[l] * ldc_cls, &dc, -1, cls[l]) ||
+        g.alloc(bn[l], (size_t)B * npix[l] * ldc_box, &db, -1, box[l])) return 1;
+    p.cls[l] = dc; p.box[l] = db; p.npix[l] = npix[l]; p.anchor_off[l] = tot; tot += npix[l] * 9;
+  }
+  p.anchor_off[5] = tot;
+  p.ldc_cls = ldc_cls; p.ldc_box = ldc_box; p.ncls = ncls; p.B = B; p.k = k; p.max_out = max_out;
+  p.score_thresh = score_thresh; p.iou_thresh = iou_thresh; p.image_scale = image_scale;
+  const size_t nlog = (size_t)tot * ncls;
+  float* da;
+  if (g.alloc("anchors", (size_t)tot * 4, &da, -1, anchors) || g.alloc("keys", nlog, &p.keys) ||
+      g.alloc("hist", 256, &p.hist, 0) || g.alloc("state", 5, &p.state, 0) || g.alloc("sel", (size_t)B * k, &p.sel) ||
+      g.alloc("cand_boxes", (size_t)B * k * 4, &p.cand_boxes) || g.alloc("cand_scores", (size_t)B * k, &p.cand_scores) ||
+      g.alloc("cand_cls", (size_t)B * k, &p.cand_cls) || g.alloc("cand_lvl", (size_t)B * k, &p.cand_lvl) ||
+      g.alloc("out_boxes", (size_t)B * max_out * 4, &p.out_boxes) || g.alloc("out_scores", (size_t)B * max_out, &p.out_scores) ||
+      g.alloc("out_labels", (size_t)B * max_out, &p.out_labels) || g.alloc("out_levels", (size_t)B * max_out, &p.out_levels) ||
+      g.alloc("out_valid", (size_t)B, &p.out_valid)) return 1;
+  p.anchors = da;
+  if (launch_effdet_post(p, nullptr)) return 1;
+  if (g.check("odt_op_effdet_post")) return 1;
+  {   // every one of the k slots per image must hold a selected key (a slot the compaction missed decodes as class -1)
+    std::vector<int32_t> cc((size_t)B * k);
+    if (get_dev(cc.data(), p.cand_cls, cc.size())) return 1;
+    for (size_t i = 0; i < cc.size(); ++i)
+      ODT_CHECK(cc[i] >= 0 && cc[i] < ncls, "odt_op_effdet_post: top-k slot " + std::to_string(i % k) + " of image " +
+                                                std::to_string(i / k) + " was not filled by the selection");
+  }
+  if (cand_idx != nullptr) {      // the selected (anchor * ncls + class) indices, sorted here by their keys: the set in reference order
+    std::vector<unsigned long long> sel((size_t)B * k);
+    if (get_dev(sel.data(), p.sel, sel.size())) return 1;
+    for (int b = 0; b < B; ++b) {
+      std::sort(sel.begin() + (size_t)b * k, sel.begin() + (size_t)(b + 1) * k, std::greater<unsigned long long>());
+      for (int i = 0; i < k; ++i) cand_idx[(size_t)b * k + i] = (int32_t)(0xFFFFFFFFu - (unsigned)sel[(size_t)b * k + i]);
+    }
+  }
+  if (get_dev(cand_boxes, p.cand_boxes, (size_t)B * k * 4) || get_dev(cand_scores, p.cand_scores, (size_t)B * k) ||
+      get_dev(cand_cls, p.cand_cls, (size_t)B * k) || get_dev(cand_lvl, p.cand_lvl, (size_t)B * k)) return 1;
+  if (get_dev(boxes, p.out_boxes, (size_t)B * max_out * 4) || get_dev(scores, p.out_scores, (size_t)B * max_out) ||
+      get_dev(labels, p.out_labels, (size_t)B * max_out) || get_dev(levels, p.out_levels, (size_t)B * max_out)) return 1;
+  return get_dev(valid, p.out_valid, (size_t)B);
+}
+
+int odt_op_preprocess_rgb(int device, const void* frames, int dtype, int B, int Hs, int Ws, int Hr, int Wr, int pad_t,
+                          int pad_l, int Hp, int Wp, int resize, float* out) {
+  ODT_CHECK(frames && out, "odt_op_preprocess_rgb: null argument");
+  ODT_CHECK(dtype == ODT_DTYPE_U8 || dtype == ODT_DTYPE_F32, "preprocess: dtype must be ODT_DTYPE_U8 or ODT_DTYPE_F32");
+  ODT_CHECK(B >= 1 && Hs >= 1 && Ws >= 1 && Hp >= 1 && Wp >= 1 && (!resize || (Hr >= 1 && Wr >= 1)), "odt_op_preprocess_rgb: bad sizes");
+  if (set_dev(device)) return 1;
+  GBufs g;
+  unsigned char* df;
+  float* dout;
+  if (g.alloc("frames", (size_t)B * Hs * Ws * 3 * (dtype == ODT_DTYPE_U8 ? 1 : 4), &df, -1, frames) ||
+      g.alloc("out", (size_t)B * Hp * Wp * 4, &dout)) return 1;
+  if (resize ? launch_preprocess_rgb_resize(df, dtype, B, Hs, Ws, Hr, Wr, pad_t, pad_l, Hp, Wp, dout, nullptr)
+             : launch_preprocess_rgb(df, dtype, B, Hs, Ws, pad_t, pad_l, Hp, Wp, dout, nullptr)) return 1;
+  if (g.check("odt_op_preprocess_rgb")) return 1;
+  return get_dev(out, dout, (size_t)B * Hp * Wp * 4);
 }
 
 }  // extern "C"

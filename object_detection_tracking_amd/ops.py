@@ -215,3 +215,148 @@ def nn_cosine(gallery, seg_offsets, dets, lib=None, device=0):
   lib.check(lib.dll.odt_nn_cosine(device, fptr(g), iptr(s), T, fptr(d), N, d.shape[1],
                                   cost.ctypes.data_as(_lib.c_double_p)))
   return cost
+
+
+# ---- EfficientDet kernels alone.  Each call reports a write past the end of any buffer it allocated (guard regions).
+
+def _se_args(se_w):
+  """(se, mid, w1, b1, w2t, b2) for the fused squeeze, or zeros / Nones without it.  se_w = (w1 [se,ldc], b1 [se],
+  w2t [se,ldc], b2 [mid])."""
+  if se_w is None:
+    return 0, 0, None, None, None, None
+  w1, b1, w2t, b2 = (f32(a) for a in se_w)
+  return w1.shape[0], b2.shape[0], w1, b1, w2t, b2
+
+
+def _p(a):
+  return fptr(a) if a is not None else None
+
+
+def dwconv(x, wt, bias, k, stride, pad_t, pad_l, out_hw, act=0, se_w=None, lib=None, device=0):
+  """depthwise k x k conv (dwconv_plan + launch_dwconv) of x [B,H,W,ldc] with wt [k*k,ldc], bias [ldc] -> out
+  [B,Ho,Wo,ldc].  se_w: the fused squeeze and the gate from its partial sums (see _se_args).  Returns (out, info) or
+  (out, mean, gate, info); info = dict(px, nsplit, xcd_bands, cqn) as the plan chose them."""
+  lib = _L(lib)
+  x = f32(x); wt = f32(wt); bias = f32(bias)
+  B, H, W, ldc = x.shape
+  Ho, Wo = out_hw
+  se, mid, w1, b1, w2t, b2 = _se_args(se_w)
+  out = np.empty((B, Ho, Wo, ldc), np.float32)
+  mean = np.empty((B, ldc), np.float32) if se_w is not None else None
+  gate = np.empty((B, ldc), np.float32) if se_w is not None else None
+  info = np.zeros(4, np.int32)
+  lib.check(lib.dll.odt_op_dwconv(device, fptr(x), B, H, W, ldc, fptr(wt), fptr(bias), k, stride, pad_t, pad_l, Ho, Wo,
+                                  act, 0, None, se, mid, _p(w1), _p(b1), _p(w2t), _p(b2), fptr(out), _p(mean), _p(gate),
+                                  iptr(info)))
+  info = dict(px=int(info[0]), nsplit=int(info[1]), xcd_bands=int(info[2]), cqn=int(info[3]))
+  return (out, info) if se_w is None else (out, mean, gate, info)
+
+
+def dwconv_maps(maps, wt, bias, k, act=0, lib=None, device=0):
+  """the multi-map depthwise launch (batch 1, stride 1, 'SAME' pads k // 2): maps = list of up to 5 [h,w,ldc] arrays.
+  Returns ([out_i], info)."""
+  lib = _L(lib)
+  maps = [f32(m) for m in maps]
+  ldc = maps[0].shape[2]
+  hw = i32([m.shape[:2] for m in maps])
+  x = np.ascontiguousarray(np.concatenate([m.reshape(-1) for m in maps]))
+  out = np.empty_like(x)
+  info = np.zeros(4, np.int32)
+  p = k // 2
+  lib.check(lib.dll.odt_op_dwconv(device, fptr(x), 1, 0, 0, ldc, fptr(f32(wt)), fptr(f32(bias)), k, 1, p, p, 0, 0, act,
+                                  len(maps), iptr(hw), 0, 0, None, None, None, None, fptr(out), None, None, iptr(info)))
+  outs, off = [], 0
+  for m in maps:
+    outs.append(out[off:off + m.size].reshape(m.shape)); off += m.size
+  return outs, dict(px=int(info[0]), nsplit=int(info[1]), xcd_bands=int(info[2]), cqn=int(info[3]))
+
+
+def se_gate(x, mid, se_w, scale=False, lib=None, device=0):
+  """squeeze-excite gate from the activations (launch_se_gate) of x [B,H*W,ldc]: returns (mean [B,ldc], gate [B,ldc],
+  x * gate [B,HW,ldc] or None, channel-sum pixel splits)."""
+  lib = _L(lib)
+  x = f32(x)
+  B, HW, ldc = x.shape
+  w1, b1, w2t, b2 = (f32(a) for a in se_w)
+  assert b2.shape[0] == mid
+  mean = np.empty((B, ldc), np.float32); gate = np.empty((B, ldc), np.float32)
+  scaled = np.empty_like(x) if scale else None
+  info = np.zeros(1, np.int32)
+  lib.check(lib.dll.odt_op_se_gate(device, fptr(x), B, HW, ldc, mid, w1.shape[0], fptr(w1), fptr(b1), fptr(w2t), fptr(b2),
+                                   fptr(mean), fptr(gate), _p(scaled), iptr(info)))
+  return mean, gate, scaled, int(info[0])
+
+
+def bifpn_fuse(inputs, modes, out_hw, pads=None, wsm=None, act=0, lib=None, device=0):
+  """BiFPN node input fusion (launch_bifpn_fuse): inputs = list of 1..3 [B,h,w,ldc] arrays, modes[k] 0 same size /
+  1 nearest resize / 2 3x3 s2 'SAME' max pool (pads[k] = (top, left)), wsm = raw 'fastattn' scalars or None (sum)."""
+  lib = _L(lib)
+  ins = [f32(a) for a in inputs]
+  n = len(ins)
+  B, _, _, ldc = ins[0].shape
+  h, w = out_hw
+  arr = (c_float_p * 3)(*[fptr(a) for a in ins])
+  hw = i32([a.shape[1:3] for a in ins])
+  md = i32(modes)
+  pd = i32(pads if pads is not None else [(0, 0)] * n)
+  ws = f32(wsm) if wsm is not None else None
+  out = np.empty((B, h, w, ldc), np.float32)
+  lib.check(lib.dll.odt_op_bifpn_fuse(device, n, arr, iptr(hw), iptr(md), iptr(pd), _p(ws), act, B, h, w, ldc, fptr(out)))
+  return out
+
+
+def mbconv_expand_dw(x, e_wt, e_bias, dw_wt, dw_bias, k, stride, pad_t, pad_l, out_hw, se_w=None, lib=None, device=0):
+  """the fused MBConv front half (launch_mbconv_expand_dw) of x [B,H,W,in_ldc]: e_wt [mid,in_ldc], e_bias [mid],
+  dw_wt [k*k,lmid], dw_bias [lmid] -> out [B,Ho,Wo,lmid] (+ mean, gate with se_w).  Returns (out, [mean, gate,] nsplit)."""
+  lib = _L(lib)
+  x = f32(x); e_wt = f32(e_wt); e_bias = f32(e_bias); dw_wt = f32(dw_wt); dw_bias = f32(dw_bias)
+  B, H, W, in_ldc = x.shape
+  mid, lmid = e_wt.shape[0], dw_wt.shape[1]
+  Ho, Wo = out_hw
+  se, _, w1, b1, w2t, b2 = _se_args(se_w)
+  out = np.empty((B, Ho, Wo, lmid), np.float32)
+  mean = np.empty((B, lmid), np.float32) if se_w is not None else None
+  gate = np.empty((B, lmid), np.float32) if se_w is not None else None
+  info = np.zeros(1, np.int32)
+  lib.check(lib.dll.odt_op_mbconv_expand_dw(device, fptr(x), B, H, W, in_ldc, fptr(e_wt), fptr(e_bias), mid, lmid,
+                                            fptr(dw_wt), fptr(dw_bias), k, stride, pad_t, pad_l, Ho, Wo, se, _p(w1), _p(b1),
+                                            _p(w2t), _p(b2), fptr(out), _p(mean), _p(gate), iptr(info)))
+  return (out, int(info[0])) if se_w is None else (out, mean, gate, int(info[0]))
+
+
+def effdet_post(cls, box, anchors, ncls, k, max_out, score_thresh=0.0, iou_thresh=0.5, image_scale=1.0, lib=None,
+                device=0):
+  """the EfficientDet detection tail (launch_effdet_post): cls / box = 5 per-level [B,npix,ldc_cls] / [B,npix,ldc_box]
+  arrays (9 * ncls / 36 valid channels), anchors [N,4].  Returns a dict: cand_idx, cand_boxes, cand_scores, cand_cls,
+  cand_lvl ([B,k(,4)]) and boxes, scores, labels, levels ([B,max_out(,4)]), valid [B]."""
+  lib = _L(lib)
+  cls = [f32(a) for a in cls]; box = [f32(a) for a in box]
+  B, _, ldc_cls = cls[0].shape
+  ldc_box = box[0].shape[2]
+  npix = i32([a.shape[1] for a in cls])
+  an = f32(anchors)
+  r = dict(cand_idx=np.empty((B, k), np.int32), cand_boxes=np.empty((B, k, 4), np.float32),
+           cand_scores=np.empty((B, k), np.float32), cand_cls=np.empty((B, k), np.int32),
+           cand_lvl=np.empty((B, k), np.int32), boxes=np.empty((B, max_out, 4), np.float32),
+           scores=np.empty((B, max_out), np.float32), labels=np.empty((B, max_out), np.int32),
+           levels=np.empty((B, max_out), np.int32), valid=np.empty(B, np.int32))
+  lib.check(lib.dll.odt_op_effdet_post(device, B, ncls, iptr(npix), ldc_cls, ldc_box, (c_float_p * 5)(*[fptr(a) for a in cls]),
+                                       (c_float_p * 5)(*[fptr(a) for a in box]), fptr(an), k, max_out, score_thresh,
+                                       iou_thresh, image_scale, iptr(r["cand_idx"]), fptr(r["cand_boxes"]),
+                                       fptr(r["cand_scores"]), iptr(r["cand_cls"]), iptr(r["cand_lvl"]), fptr(r["boxes"]),
+                                       fptr(r["scores"]), iptr(r["labels"]), iptr(r["levels"]), iptr(r["valid"])))
+  return r
+
+
+def preprocess_rgb(frames, pad_t, pad_l, Hp, Wp, resize_hw=None, lib=None, device=0):
+  """the EfficientDet preprocess of BGR frames [B,Hs,Ws,3] (uint8 or float32) -> normalised RGB [B,Hp,Wp,4], zero
+  padded; resize_hw = (Hr, Wr): the on-device bilinear resize first."""
+  lib = _L(lib)
+  dtype = _lib.ODT_DTYPE_U8 if frames.dtype == np.uint8 else _lib.ODT_DTYPE_F32
+  fr = np.ascontiguousarray(frames if dtype == _lib.ODT_DTYPE_U8 else frames.astype(np.float32))
+  B, Hs, Ws, _ = fr.shape
+  Hr, Wr = resize_hw if resize_hw is not None else (0, 0)
+  out = np.empty((B, Hp, Wp, 4), np.float32)
+  lib.check(lib.dll.odt_op_preprocess_rgb(device, fr.ctypes.data_as(C.c_void_p), dtype, B, Hs, Ws, Hr, Wr, pad_t, pad_l,
+                                          Hp, Wp, int(resize_hw is not None), fptr(out)))
+  return out

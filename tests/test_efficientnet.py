@@ -234,18 +234,13 @@ def _det_e2e(lib, model, H, W, topk, score_thr=0.02, tol_box=2e-2, src_hw=None, 
     assert len(boxes) == len(rb) and len(boxes) > 3, (len(boxes), len(rb))
     # near-equal scores of random-init heads may swap two candidates (1e-6 logit differences):
     # compare as sets first, element-wise when the order is identical
-    from common import match_detections, tie_swaps
+    from common import match_detections, match_pairs, tie_swaps
     miss, extra = match_detections(boxes, labels, probs, rb, rc, rs, tol_box, 2e-5)
     # a random-init class head puts whole grids of overlapping candidates on one score plateau (differences of 1e-7):
     # which of two such NMS competitors survives is below the f32 noise of ANY implementation; those swaps are counted
     # apart, everything else keeps the budget
     ties = tie_swaps(boxes, labels, probs, rb, rc, rs, tol_box, 2e-5)
     assert (miss - ties) + (extra - ties) <= max(2, len(rb) // 25), (miss, extra, ties)
-    if miss + extra > 0 or not np.array_equal(labels, rc):
-      return
-    if np.abs(boxes - rb).max() > tol_box:       # same set, two near-equal scores in swapped order
-      return
-    np.testing.assert_allclose(probs, rs, rtol=0, atol=2e-5)
     # fpn_box_feat: ROIAlign mean on each box's own level (restated with the oracle's crop_and_resize)
     from oracle import graph as og
     want = np.zeros((len(rb), c["fpn_num_filters"]), np.float32)
@@ -253,8 +248,18 @@ def _det_e2e(lib, model, H, W, topk, score_thr=0.02, tol_box=2e-2, src_hw=None, 
       f = fpn[int(rl[i])].numpy()
       bf = (rb[i:i + 1] * np.float32(1.0 / 2 ** int(rl[i]))).astype(np.float32)
       want[i] = og.roi_align(f, bf, np.zeros((1,), np.int32), 7).mean(axis=(2, 3))[0]
-    assert feats.shape == want.shape
-    np.testing.assert_allclose(feats, want, rtol=0, atol=5e-5 * max(1.0, np.abs(want).max()))
+    assert feats.shape == (len(boxes), want.shape[1])
+    feat_tol = 5e-5 * max(1.0, np.abs(want).max())
+    # every matched pair, whatever tie swaps happened elsewhere: label, score, box and its pooled feature
+    pairs, _, _ = match_pairs(boxes, labels, probs, rb, rc, rs, tol_box, 2e-5)
+    for i, j in pairs:
+      assert labels[i] == rc[j] and abs(float(probs[i]) - float(rs[j])) <= 2e-5, (i, j, probs[i], rs[j])
+      assert np.abs(boxes[i] - rb[j]).max() <= tol_box, (i, j, boxes[i], rb[j])
+      assert np.abs(feats[i] - want[j]).max() <= feat_tol, ("fpn_box_feat", i, j, np.abs(feats[i] - want[j]).max())
+    # positionally where the order is the oracle's (same set, no swap of near-equal scores)
+    if miss + extra == 0 and np.array_equal(labels, rc) and np.abs(boxes - rb).max() <= tol_box:
+      np.testing.assert_allclose(probs, rs, rtol=0, atol=2e-5)
+      np.testing.assert_allclose(feats, want, rtol=0, atol=feat_tol)
   finally:
     m.close()
 
