@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: detector FPS @1920x1080, batch 8, per MI355X (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path (preprocess -> ResNet-101-dilated+FPN -> RPN -> proposals
@@ -9,7 +9,12 @@ A "step" is one pass of the hot path (preprocess -> ResNet-101-dilated+FPN -> RP
 batch of 8 synthetic 1920x1080 frames that are already resident in HBM (uint8).  One process
 per GPU, one video stream per GPU, weights replicated, no data-path collective (streams are
 independent: "weak" scaling; RCCL only carries the barrier and the max-over-ranks timing).
-Rank 0 prints ONE JSON line with the contract fields plus `roofline` (the conv implicit-GEMM
+
+A plain run does only what the headline needs: set up, warm up, time the steps, write
+--dump-outputs if given, and print ONE JSON line with the contract fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step) and a description of the run (handle, config, per-rank
+figures).  Everything else is behind --full (the --no-* options below thin it out):
+rank 0 then also prints `verified` / `verification`, `extra`, `roofline` (the conv implicit-GEMM
 launches, HIP-event timed on their launch stream, split by kernel family: the split kernels -- f32 convolution
 through exact 16-bit MFMA products, three f16 products per MAC on the `conv_h2` kernels, six bf16 ones on the
 `conv_split` kernels -- and the exact-f32 `conv_igemm_kernel`) and, at N=1, `cpu_baseline` (the oracle -- a CPU
@@ -45,6 +50,10 @@ def main():
   ap.add_argument("--graph", default="multi", choices=["multi", "single"],
                   help="multi = Mask_RCNN_FPN_multi (batched graph, the headline); single = Mask_RCNN_FPN (BASELINE config #2: "
                        "the b=1 graph of obj_detect_tracking.py -- min-size filter, prob > 1e-4, per-class NMS; needs --batch 1)")
+  ap.add_argument("--full", action="store_true",
+                  help="after the headline, also check the timed region against a blocking forward and run every other "
+                       "measurement: roofline, sustained MFMA peak, counter passes, the `extra` legs, the CPU baseline and "
+                       "the EfficientDet-D7 leg (the --no-* options below leave parts of it out)")
   ap.add_argument("--no-cpu-baseline", action="store_true")
   ap.add_argument("--keep-taps", action="store_true", help="A/B: a dedicated buffer per stage tensor instead of the activation arena")
   ap.add_argument("--no-d7", action="store_true", help="skip the EfficientDet-D7 leg of `extra` (BASELINE config #5)")
@@ -130,16 +139,21 @@ def main():
     raise SystemExit("bench.py: --graph single is the b=1 graph (obj_detect_tracking.py:241-242): pass --batch 1")
   cfg = make_config(rpn_test_post_nms_topk=args.topk, im_batch_size=B, max_size=max(H, W),
                     short_edge_size=min(H, W), keep_taps=bool(args.keep_taps))
-  weights = synthetic_weights(cfg, seed=0)
   S = max(1, args.streams)
-  all_models = [models.get_model(cfg, local_rank, weights=weights, is_multi=multi) for _ in range(S)]
-  engs = [m.engine(B, H, W) for m in all_models]
-  model, eng = all_models[0], engs[0]
   # one video stream per handle: each gets its own seeded frames -- NROT different batches per stream, all resident in
   # HBM, taken in turn by the steps of the timed region (frame content, recorded tensor ranges, proposal / detection
-  # counts and what the caches hold differ from one step to the next, as they do on a video)
+  # counts and what the caches hold differ from one step to the next, as they do on a video).  Each batch is its own
+  # seeded call, so they are made on worker threads (numpy leaves the GIL for the array work) while the handles are built
   NROT = max(1, args.rotate)
-  rot_frames = [[synthetic_frames(B, H, W, seed=1234 + rank + 1000 * i + 77 * r) for r in range(NROT)] for i in range(S)]
+  from concurrent.futures import ThreadPoolExecutor
+  with ThreadPoolExecutor(max_workers=min(8, S * NROT)) as pool:
+    rot_jobs = [[pool.submit(synthetic_frames, B, H, W, seed=1234 + rank + 1000 * i + 77 * r) for r in range(NROT)]
+                for i in range(S)]
+    weights = synthetic_weights(cfg, seed=0)
+    all_models = [models.get_model(cfg, local_rank, weights=weights, is_multi=multi) for _ in range(S)]
+    engs = [m.engine(B, H, W) for m in all_models]
+    rot_frames = [[job.result() for job in jobs] for jobs in rot_jobs]
+  model, eng = all_models[0], engs[0]
   frames = rot_frames[0][0]
   dev_rot = [[torch.from_numpy(f).cuda(local_rank) for f in fs] for fs in rot_frames]      # HBM-resident uint8 input
   dev_frames = dev_rot[0][0]
@@ -205,32 +219,34 @@ def main():
   rank_fps = [S * B * args.steps / t for t in rank_dts]
   dumped = dump_outputs(args.dump_outputs, engs, nn_cost) if args.dump_outputs and rank == 0 else None
 
-  # the timed region, checked: the outputs the LAST replayed forward of every stream left in HBM must equal, bit for
-  # bit, a blocking odt_forward of the same frames through the host boundary -- and must be a non-trivial detection set
-  last = (step_no[0] - 1) % NROT
-  verified = verify_timed_region(engs, [fs[last] for fs in rot_frames])
-  verified["resident_batches_rotated"] = NROT
-  verified["batch_verified"] = last
+  verified, prof, sustained = None, None, None
+  if args.full:
+    # the timed region, checked: the outputs the LAST replayed forward of every stream left in HBM must equal, bit for
+    # bit, a blocking odt_forward of the same frames through the host boundary -- and must be a non-trivial detection set
+    last = (step_no[0] - 1) % NROT
+    verified = verify_timed_region(engs, [fs[last] for fs in rot_frames])
+    verified["resident_batches_rotated"] = NROT
+    verified["batch_verified"] = last
 
-  # roofline of the dominant kernel family (implicit-GEMM conv, ~99% of the FLOPs): HIP events
-  # around every launch on the launch stream, outside the timed region.
-  nprof = max(1, args.profile_steps)
-  prof = profile_convs(eng, dev_frames.data_ptr(), nprof)
+    # roofline of the dominant kernel family (implicit-GEMM conv, ~99% of the FLOPs): HIP events
+    # around every launch on the launch stream, outside the timed region.
+    nprof = max(1, args.profile_steps)
+    prof = profile_convs(eng, dev_frames.data_ptr(), nprof)
 
-  sustained = None
-  if rank == 0:
-    sustained = sustained_peak(eng.lib, local_rank)
+    if rank == 0:
+      sustained = sustained_peak(eng.lib, local_rank)
 
-  # every rank: the PCIe-inclusive pipelined rate of its own stream (the figure that degrades with host contention when
-  # N ranks share one host; `value` above is HBM-resident) -- measured by all ranks at the same time
+  # every rank: who ran where, and (--full) the PCIe-inclusive pipelined rate of its own stream (the figure that degrades
+  # with host contention when N ranks share one host; `value` above is HBM-resident) -- measured by all ranks at the same time
   per_rank = None
   if world > 1:
     barrier()
     mine = {"rank": rank, "local_rank": local_rank, "affinity": affinity}
-    try:
-      mine.update(pipelined_leg(eng, frames, B, nbatches=6))
-    except Exception as ex:
-      mine["pipelined_failed"] = repr(ex)
+    if args.full:
+      try:
+        mine.update(pipelined_leg(eng, frames, B, nbatches=6))
+      except Exception as ex:
+        mine["pipelined_failed"] = repr(ex)
     mine["device_resident_fps"] = rank_fps[rank] if rank < len(rank_fps) else None
     gathered = [None] * world
     dist.all_gather_object(gathered, mine)
@@ -240,7 +256,7 @@ def main():
   # odt_forward -> host outputs incl. [M,256,7,7] features): PCIe-inclusive rate; (b) the DeepSORT
   # appearance matching kernel at BASELINE config #3 size (T=64 tracks x budget 5, N=100 dets).
   extra = {}
-  if rank == 0 and not args.no_extras and world == 1:        # (N > 1: the scaling runs report the timed region only)
+  if rank == 0 and args.full and not args.no_extras and world == 1:    # (N > 1: the scaling runs report the timed region only)
     try:
       from object_detection_tracking_amd import ops
       t1 = time.perf_counter()
@@ -362,10 +378,8 @@ def main():
       extra["extras_failed"] = repr(ex)
   if rank == 0:
     fps = world * S * B * args.steps / dt
-    if (B, H, W) == (8, 1080, 1920) and world == 1 and not args.no_extras and not args.no_live_traffic:
+    if args.full and (B, H, W) == (8, 1080, 1920) and world == 1 and not args.no_extras and not args.no_live_traffic:
       live_pmc_traffic()
-    roofline = conv_roofline(prof, sustained, (B, H, W) == (8, 1080, 1920))
-    fam = prof["fam"]
     out = {
         "metric": "detector FPS @%dx%d b=%d per MI355X" % (W, H, B),
         "value": fps,
@@ -374,8 +388,6 @@ def main():
         "ranks_seen": ranks_seen,
         "per_rank_fps": rank_fps,
         "per_rank": per_rank if per_rank is not None else [{"rank": 0, "local_rank": local_rank, "affinity": affinity}],
-        "verified": bool(verified.get("ok")),
-        "verification": verified,
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": 1e3 * dt / args.steps,
@@ -384,7 +396,7 @@ def main():
         "vs_baseline": None,
         "value_scope": "device-resident: uint8 frames already in HBM when the timed region starts (%d different batches per "
                        "stream, taken in turn), outputs left in HBM (the PCIe-inclusive pipelined rate and the detect+track "
-                       "rate are under `extra`)" % NROT,
+                       "rate are under `extra` of a --full run)" % NROT,
         "dtype": "f32",
         "arithmetic": arithmetic_of(eng.describe()),
         "handle": eng.describe(),      # the arithmetic mode / kernel families as the handle itself reports them
@@ -397,14 +409,17 @@ def main():
                                 W, H, B, args.topk),
                    "graph": "Mask_RCNN_FPN_multi" if multi else "Mask_RCNN_FPN", "streams_per_gpu": S,
                    "nn_matching_calls_in_timed_and_warmup_steps": nn_calls[0]},
-        "roofline": roofline,
     }
-    out["extra"] = extra
+    if args.full:
+      out["verified"] = bool(verified.get("ok"))
+      out["verification"] = verified
+      out["roofline"] = conv_roofline(prof, sustained, (B, H, W) == (8, 1080, 1920))
+      out["extra"] = extra
     if dumped is not None:
       out["dump_outputs"] = dumped
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
       out["cpu_baseline"] = cpu_baseline(cfg, weights, frames, args.cpu_frames, multi)
-    if world == 1 and S == 1 and not args.no_extras and not args.no_d7 and (B, H, W) == (8, 1080, 1920):
+    if args.full and world == 1 and S == 1 and not args.no_extras and not args.no_d7 and (B, H, W) == (8, 1080, 1920):
       # (g) BASELINE config #5: EfficientDet-D7 at 1536 x 1536 + the TMOT tracker, its own roofline (HBM) and CPU baseline
       # (in a child process with a time limit: whatever happens there, the headline line above is printed)
       for m in all_models:
@@ -559,7 +574,7 @@ def live_pmc_traffic(timeout_s=100):
     d = tempfile.mkdtemp(prefix="odt_pmc_")
     try:
       cmd = [exe, "--kernel-trace", "--pmc", ctr, "--output-format", "csv", "-d", d, "-o", "pmc", "--", sys.executable,
-             os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--no-d7",
+             os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras", "--no-d7",
              "--profile-steps", "1", "--no-live-traffic"]
       env = dict(os.environ); env.setdefault("TMPDIR", "/tmp")
       subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=timeout_s, check=True)

@@ -1,4 +1,4 @@
-run() { env $1 timeout 400 python bench.py --no-extras --no-cpu-baseline --no-d7 --batch $2 --streams $3 --steps 20 --warmup 3 2>/dev/null | tail -1 | python -c "
+run() { env $1 timeout 400 python bench.py --full --no-extras --no-cpu-baseline --no-d7 --batch $2 --streams $3 --steps 20 --warmup 3 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 print('%.2f FPS  %.3f ms/step verified %s fused %s' % (d['value'], d['ms_per_step'], d.get('verified'), d.get('handle',{}).get('bottleneck_tails_fused')))"; }

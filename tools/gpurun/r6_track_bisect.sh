@@ -1,5 +1,6 @@
 #!/bin/bash
-mkdir -p gpurun_out
+OUT=${OUT:-out}
+mkdir -p $OUT
 export TMPDIR=/tmp
 R=$(pwd)
 line() { python -c "
@@ -7,5 +8,5 @@ import sys,json; d=json.load(sys.stdin); e=d['extra']; print('value %.1f' % d['v
 cd $R/wt_r05; echo "[r05 tree] $(timeout 600 python bench.py --steps 10 --warmup 2 --no-d7 --no-cpu-baseline 2>/dev/null | tail -1 | line)"
 cd $R
 for v in "X=1" "ODT_RANGE_HOST=0" "ODT_STAGE_FRAMES=0" "ODT_NO_WATCH=1" "ODT_RANGE_HOST=0 ODT_STAGE_FRAMES=0 ODT_NO_WATCH=1 ODT_RANGE_STATS=0"; do
-echo "[r06 $v] $(env $v timeout 600 python bench.py --steps 10 --warmup 2 --no-d7 --no-cpu-baseline --no-live-traffic 2>/dev/null | tail -1 | line)"
+echo "[r06 $v] $(env $v timeout 600 python bench.py --full --steps 10 --warmup 2 --no-d7 --no-cpu-baseline --no-live-traffic 2>/dev/null | tail -1 | line)"
 done

@@ -28,7 +28,7 @@ ws, _ = agg(load("WRITE_SIZE"), is_split)
 ms, _ = agg(load("SQ_VALU_MFMA"), is_split)
 _, nfwd = agg(load("FETCH_SIZE"), is_pre)
 res = {
-  "command": "rocprofv3 --kernel-trace --pmc <set> --output-format csv -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --profile-steps 1",
+  "command": "rocprofv3 --kernel-trace --pmc <set> --output-format csv -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --profile-steps 1",
   "forwards_profiled": nfwd, "conv_launches": nconv,
   "conv_fetch_GB_per_forward_raw": f["FETCH_SIZE"] * 1024 / nfwd / 1e9,
   "conv_write_GB_per_forward_raw": w["WRITE_SIZE"] * 1024 / nfwd / 1e9,
