@@ -179,6 +179,40 @@ int odt_read_outputs(odt_handle h, odt_outputs* out);
  * in the reference.  Pass the plan's own size to switch back.  No tickets may be in flight. */
 int odt_set_source_size(odt_handle h, int src_height, int src_width);
 
+/* Number of forwards enqueued on the handle so far (odt_forward, odt_forward_async, odt_submit*): the serial of the most
+ * recent one, which odt_mask_rle checks. */
+int odt_forward_serial(odt_handle h, int64_t* serial);
+
+/* Masks as COCO run-length encodings of the frame (reference obj_detect_tracking.py:715-739, obj_detect_imgs.py:504-527:
+ * final_boxes / scale, fill_full_mask(box, mask, im.shape[:2]) (nn.py:1565-1584), pycocotools mask.encode of the frame in
+ * column-major order, counts.decode("ascii")).  Per detection j: b = boxes[j] / (float)scale in f32; x0 = (int)(b0 + 0.5f),
+ * y0 = (int)(b1 + 0.5f), x1 = max(x0, (int)(b2 - 0.5f)), y1 = max(y0, (int)(b3 - 0.5f)); the 28x28 mask resized to
+ * (y1 + 1 - y0) x (x1 + 1 - x0) with the INTER_LINEAR rule of the ingest resize (pixel centres (i + 0.5) * src / dst - 0.5,
+ * taps clamped, weights (1 - f, f), the horizontal pass first), thresholded with > 0.5, pasted at [y0..y1] x [x0..x1] of an
+ * all-zero height x width frame.  Deviation: where the reference raises (a rectangle reaching past the frame, a sub-pixel
+ * effect of the averaged scale), the rectangle is clipped to the frame.  The encoding runs on the device (csrc/mask_rle.hip);
+ * at most 32 * width + 1 run boundaries per detection, and a detection past that bound fails the call with its index.
+ * Result memory belongs to the library: valid until the next call of the same entry point on the same handle
+ * (odt_mask_rle) or on the calling thread (odt_op_mask_rle).
+ *   strings        the n compressed strings back to back (pycocotools rleToString, no terminators)
+ *   offsets [n]    byte offset of detection j's string; lengths [n] its length
+ *   counts         want_counts != 0: the uncompressed counts of all n detections back to back (else NULL);
+ *   count_offsets [n + 1] where detection j's counts start */
+typedef struct odt_rle_result {
+  int32_t n;
+  int32_t height, width;
+  const char* strings;
+  const int64_t* offsets;
+  const int32_t* lengths;
+  const uint32_t* counts;
+  const int64_t* count_offsets;
+} odt_rle_result;
+/* The masks of the handle's forward number `serial` (odt_forward_serial): final_masks / final_boxes of the valid detections
+ * as they are on the device, on the stream that forward ended on.  Fails if another forward has been enqueued since (its
+ * outputs replace that frame's) and for a handle built without add_mask.  height x width: the frame the boxes are mapped
+ * to, scale: what the driver divides the boxes by (1 for frames of the plan's size). */
+int odt_mask_rle(odt_handle h, int64_t serial, int height, int width, double scale, int want_counts, odt_rle_result* out);
+
 /* Pipelined ingest (replaces the frame.astype(float32) + feed_dict copy of
  * obj_detect_tracking.py:597-635 and the prefetch queue of enqueuer_thread.py:236-303 on the
  * device side): two slots of pinned host staging + device input + pinned output staging.
@@ -434,6 +468,11 @@ int odt_op_effdet_post(int device, int B, int ncls, const int32_t* npix, int ldc
  * f32); resize = 1: bilinear TF-1.x resize to [Hr,Wr] first (launch_preprocess_rgb_resize), 0: launch_preprocess_rgb. */
 int odt_op_preprocess_rgb(int device, const void* frames, int dtype, int B, int Hs, int Ws, int Hr, int Wr, int pad_t,
                           int pad_l, int Hp, int Wp, int resize, float* out);
+
+/* odt_mask_rle on caller-supplied masks [n,28,28] and boxes [n,4] (network coordinates), host pointers, or device pointers
+ * when on_device != 0.  The transition, size, string and count buffers (and the input copies) end in guard regions. */
+int odt_op_mask_rle(int device, const float* masks, const float* boxes, int n, int on_device, int height, int width,
+                    double scale, int want_counts, odt_rle_result* out);
 
 #ifdef __cplusplus
 }

@@ -51,6 +51,28 @@ class OdtOutputs(C.Structure):
               ("masks", c_float_p)]
 
 
+class OdtRleResult(C.Structure):
+  _fields_ = [("n", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("strings", C.c_void_p),
+              ("offsets", c_i64_p), ("lengths", c_int_p), ("counts", C.POINTER(C.c_uint32)), ("count_offsets", c_i64_p)]
+
+  def rles(self):
+    """[{"size": [H, W], "counts": str}] -- what the reference puts into its JSON (counts.decode("ascii"))."""
+    size = [int(self.height), int(self.width)]
+    out = []
+    for j in range(int(self.n)):
+      s = C.string_at(self.strings + int(self.offsets[j]), int(self.lengths[j])) if self.lengths[j] else b""
+      out.append({"size": list(size), "counts": s.decode("ascii")})
+    return out
+
+  def count_lists(self):
+    """The uncompressed counts per detection (want_counts) as numpy uint32 arrays."""
+    if not self.counts:
+      return None
+    total = int(self.count_offsets[int(self.n)])
+    flat = np.ctypeslib.as_array(self.counts, shape=(total,)).copy() if total else np.zeros(0, np.uint32)
+    return [flat[int(self.count_offsets[j]):int(self.count_offsets[j + 1])] for j in range(int(self.n))]
+
+
 def fptr(a):
   return a.ctypes.data_as(c_float_p)
 
@@ -84,7 +106,7 @@ class OdtLib(object):
       "odt_op_maxpool", "odt_op_topk", "odt_op_nms", "odt_op_proposals",
       "odt_op_roi_align", "odt_op_detections", "odt_op_class_nms",
       "odt_op_dwconv", "odt_op_se_gate", "odt_op_bifpn_fuse", "odt_op_mbconv_expand_dw", "odt_op_effdet_post",
-      "odt_op_preprocess_rgb", "odt_tracker_create", "odt_tracker_destroy",
+      "odt_op_preprocess_rgb", "odt_forward_serial", "odt_mask_rle", "odt_op_mask_rle", "odt_tracker_create", "odt_tracker_destroy",
       "odt_tracker_predict", "odt_tracker_update", "odt_tracker_tracks", "odt_lsap", "odt_tracker_nms",
       "odt_tmot_create", "odt_tmot_destroy", "odt_tmot_reset", "odt_tmot_update", "odt_tmot_tracks",
   ]
@@ -181,6 +203,10 @@ class OdtLib(object):
                                      c_float_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, c_int_p, c_float_p,
                                      c_float_p, c_int_p, c_int_p, c_float_p, c_float_p, c_int_p, c_int_p, c_int_p]
     d.odt_op_preprocess_rgb.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 11 + [c_float_p]
+    d.odt_forward_serial.argtypes = [C.c_void_p, c_i64_p]
+    d.odt_mask_rle.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(OdtRleResult)]
+    d.odt_op_mask_rle.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                  C.POINTER(OdtRleResult)]
 
   def check(self, rc):
     if rc != 0:

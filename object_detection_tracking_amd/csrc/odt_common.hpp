@@ -6,6 +6,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <string>
 
 #include "knobs.hpp"
@@ -378,6 +379,38 @@ struct MaskSelectParams {
   float* masks;          // [R_cap,28,28]
 };
 int launch_mask_select(const MaskSelectParams& p, hipStream_t stream);
+
+// ------------------------------------------------------- mask paste + COCO RLE (mask_rle.hip; obj_detect_tracking.py:715-739)
+constexpr int kRleMaxH = 4096;         // frame rows (one LDS row-tap table per workgroup)
+constexpr int kRleTransPerCol = 32;    // static bound: run boundaries per detection <= 32 * W0 + 1
+struct MaskRleParams {
+  const float* masks;    // [R,28,28] final_masks
+  const float* boxes;    // [R,4] x1,y1,x2,y2 in network coordinates
+  const int* valid;      // device count of detections (rows >= it produce nothing) or nullptr: n
+  int R, n;
+  int H0, W0;            // frame size
+  float scale;           // boxes / scale = frame coordinates
+  int cap;               // transitions per detection: kRleTransPerCol * W0 + 1
+  int* trans;            // [R,cap] column-major run boundaries
+  int* ntrans;           // [R] their number, -1 past the bound
+  int* slen;             // [R] bytes of the compressed string
+  char* str;             // the strings, packed in detection order
+  unsigned* counts;      // the counts, packed (or nullptr)
+};
+int launch_mask_rle_runs(const MaskRleParams& p, hipStream_t stream);
+int launch_mask_rle_strings(const MaskRleParams& p, hipStream_t stream);
+// host result of one call (odt_rle_result points into it)
+struct MaskRleHost {
+  int n = 0, H0 = 0, W0 = 0;
+  std::vector<char> str;
+  std::vector<int64_t> off, coff;
+  std::vector<int32_t> len;
+  std::vector<uint32_t> counts;
+};
+// device buffer by name and size in bytes (a handle's persistent buffers, or the guarded buffers of odt_op_mask_rle)
+typedef std::function<int(const char* name, size_t bytes, void** dev)> RleAlloc;
+// runs kernel -> sizes to the host -> strings kernel -> strings (and counts) to the host, all on `st`
+int run_mask_rle(MaskRleParams p, bool want_counts, hipStream_t st, const RleAlloc& alloc, MaskRleHost& out);
 
 // ------------------------------------------------------- detection tail (K11,K12,K13)
 struct DetectParams {

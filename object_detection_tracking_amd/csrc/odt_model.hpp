@@ -136,6 +136,8 @@ struct odt_model {
   unsigned long long forwards_enqueued = 0;
   int eff_scaled_h = 0, eff_scaled_w = 0;   // EfficientDet: size of the resized frame inside the padded input
   float* final_masks = nullptr;   // [B*per_im, 28, 28] (add_mask)
+  std::map<std::string, std::unique_ptr<DevBuf>> rle_bufs;   // odt_mask_rle: device buffers by name, grown on demand
+  MaskRleHost rle_host;                                       // ... and the result of its last call
   DetectParams det{};
   Tensor image_pad, frames_dev;
   int src_h = 0, src_w = 0;          // source frame size (== cfg.height/width unless odt_set_source_size)
@@ -228,6 +230,14 @@ int build_plan(odt_model* m);
 int build_plan_effnet(odt_model* m);
 // ---- runtime.hip
 int run_plan(odt_model* m, const void* frames, int dtype, int on_device, hipStream_t st);
+
+// odt_rle_result view of a mask_rle host result
+inline void rle_fill(const MaskRleHost& h, odt_rle_result* r) {
+  r->n = h.n; r->height = h.H0; r->width = h.W0;
+  r->strings = h.str.data(); r->offsets = h.off.data(); r->lengths = h.len.data();
+  r->counts = h.counts.empty() ? nullptr : h.counts.data();
+  r->count_offsets = h.coff.data();
+}
 
 // every device pointer op `oi` reads or writes, as a mutable reference (plan_arena: liveness, then the rewrite)
 template <typename F>

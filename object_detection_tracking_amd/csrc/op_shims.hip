@@ -786,4 +786,30 @@ int odt_op_preprocess_rgb(int device, const void* frames, int dtype, int B, int 
   return get_dev(out, dout, (size_t)B * Hp * Wp * 4);
 }
 
+int odt_op_mask_rle(int device, const float* masks, const float* boxes, int n, int on_device, int height, int width,
+                    double scale, int want_counts, odt_rle_result* out) {
+  ODT_CHECK(out != nullptr && (n == 0 || (masks && boxes)), "odt_op_mask_rle: null argument");
+  ODT_CHECK(n >= 0, "odt_op_mask_rle: bad number of detections");
+  if (set_dev(device)) return 1;
+  static thread_local MaskRleHost res;      // (the result stays readable until this thread's next call)
+  GBufs g;
+  MaskRleParams p; std::memset(&p, 0, sizeof(p));
+  p.masks = masks; p.boxes = boxes;
+  if (!on_device && n > 0) {
+    float *dm, *db;
+    if (g.alloc("masks", (size_t)n * 784, &dm, -1, masks) || g.alloc("boxes", (size_t)n * 4, &db, -1, boxes)) return 1;
+    p.masks = dm; p.boxes = db;
+  }
+  p.R = n; p.n = n; p.H0 = height; p.W0 = width; p.scale = (float)scale;
+  auto alloc = [&g](const char* name, size_t bytes, void** dev) -> int {
+    unsigned char* d;
+    if (g.alloc(name, bytes, &d)) return 1;
+    *dev = d;
+    return 0;
+  };
+  if (run_mask_rle(p, want_counts != 0, nullptr, alloc, res) || g.check("odt_op_mask_rle")) return 1;
+  rle_fill(res, out);
+  return 0;
+}
+
 }  // extern "C"

@@ -436,6 +436,38 @@ int odt_read_outputs(odt_handle h, odt_outputs* out) {
   return 0;
 }
 
+int odt_forward_serial(odt_handle h, int64_t* serial) {
+  ODT_CHECK(h != nullptr && serial != nullptr, "null argument");
+  *serial = (int64_t)h->forwards_enqueued;
+  return 0;
+}
+
+int odt_mask_rle(odt_handle h, int64_t serial, int height, int width, double scale, int want_counts, odt_rle_result* out) {
+  ODT_CHECK(h != nullptr && out != nullptr, "null argument");
+  ODT_CHECK(h->final_masks != nullptr, "odt_mask_rle: the model was built without add_mask");
+  ODT_CHECK(h->finalized && h->forwards_enqueued > 0, "odt_mask_rle: no forward has been enqueued on this handle");
+  ODT_CHECK(serial == (int64_t)h->forwards_enqueued,
+            "odt_mask_rle: forward " + std::to_string(serial) + " is not the handle's most recent one (" +
+                std::to_string(h->forwards_enqueued) + "): its masks have been replaced");
+  ODT_HIP(hipSetDevice(h->device));
+  MaskRleParams p; std::memset(&p, 0, sizeof(p));
+  p.masks = h->final_masks; p.boxes = h->det.out_boxes; p.valid = h->det.out_valid;
+  p.R = h->cfg.result_per_im; p.H0 = height; p.W0 = width; p.scale = (float)scale;
+  auto alloc = [h](const char* name, size_t bytes, void** dev) -> int {
+    std::unique_ptr<DevBuf>& b = h->rle_bufs[name];
+    if (!b || b->bytes < bytes) {
+      b.reset(new DevBuf());
+      if (b->alloc(bytes)) return 1;
+    }
+    *dev = b->p;
+    return 0;
+  };
+  // (on the stream the forward's tail ran on: the kernels see its final_masks / final_boxes)
+  if (run_mask_rle(p, want_counts != 0, h->done_stream, alloc, h->rle_host)) return 1;
+  rle_fill(h->rle_host, out);
+  return 0;
+}
+
 static int slot_prepare(odt_handle h, odt_model::Slot& sl, size_t in_bytes) {
   const odt_config& cfg = h->cfg;
   const size_t B = cfg.batch, per = cfg.result_per_im, FC = cfg.fpn_channels;

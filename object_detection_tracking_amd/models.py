@@ -194,7 +194,7 @@ class _Engine(object):
   def __getattribute__(self, name):
     # a closed engine (model.close(), or evicted from the model's plan cache) fails loudly instead of passing a null handle
     if name in ("forward", "submit", "collect", "read_outputs", "forward_device_async", "tap", "set_source_size",
-                "profile", "describe") and object.__getattribute__(self, "h") is None:
+                "profile", "describe", "forward_serial", "mask_rle") and object.__getattribute__(self, "h") is None:
       raise _lib.OdtError("engine closed (model.close(), or evicted from the model's plan cache: _DetectorBase.max_engines)")
     return object.__getattribute__(self, name)
 
@@ -341,6 +341,23 @@ class _Engine(object):
                                             C.byref(out)))
     self._watch()
     return self._result(want_feats, want_pooled)
+
+  def forward_serial(self):
+    """odt_forward_serial: the number of forwards enqueued on this engine's handle (the serial of the most recent one)."""
+    v = C.c_int64()
+    self.lib.check(self.lib.dll.odt_forward_serial(self.h, C.byref(v)))
+    return int(v.value)
+
+  def mask_rle(self, frame_hw, scale, serial=None, want_counts=False):
+    """odt_mask_rle: the masks of forward ``serial`` (default: the most recent one) as COCO RLE of a frame_hw frame with the
+    boxes divided by ``scale`` -- [{"size": [H0, W0], "counts": str}] per valid detection (reference
+    obj_detect_tracking.py:715-739).  Raises once another forward has been enqueued since ``serial``."""
+    res = _lib.OdtRleResult()
+    s = self.forward_serial() if serial is None else int(serial)
+    self.lib.check(self.lib.dll.odt_mask_rle(self.h, s, int(frame_hw[0]), int(frame_hw[1]), float(scale),
+                                             int(bool(want_counts)), C.byref(res)))
+    rles = res.rles()
+    return (rles, res.count_lists()) if want_counts else rles
 
   def read_outputs(self, want_feats=True, want_pooled=False):
     """The outputs of the most recently enqueued forward (odt_read_outputs): what :meth:`forward` would have
@@ -629,8 +646,21 @@ class Mask_RCNN_FPN(_DetectorBase):
                                                        want_pooled=pooled)
     r = int(valid[0])
     self.last_masks = e._masks[:r].copy() if e.add_mask else None    # final_masks [R,28,28]
+    self._last_forward = (e, e.forward_serial())
     return (boxes[0, :r].copy(), labels[0, :r].astype(np.int64), probs[0, :r].copy(),
             pl if pooled else feats)
+
+  def masks_rle(self, frame_hw, scale, want_counts=False):
+    """The masks of the last ``predict`` / ``predict_raw`` as the reference's JSON holds them: per detection
+    ``{"size": [H0, W0], "counts": str}`` of ``fill_full_mask(final_boxes[j] / scale, final_masks[j], frame_hw)`` encoded
+    with pycocotools (obj_detect_tracking.py:715-739), computed on the device from that forward's outputs.  A rectangle
+    that reaches past the frame is clipped to it (the reference raises).  Raises if the engine has run another forward
+    since, and for a model without add_mask."""
+    last = getattr(self, "_last_forward", None)
+    if last is None:
+      raise _lib.OdtError("masks_rle: no forward yet (predict / predict_raw)")
+    e, serial = last
+    return e.mask_rle(frame_hw, scale, serial=serial, want_counts=want_counts)
 
   def predict_stream(self, frames, in_flight=2, pooled=False):
     """Frame-by-frame detection of a video with ``in_flight`` consecutive frames on the GPU at once (round 6): frame t runs on
@@ -659,19 +689,23 @@ class Mask_RCNN_FPN(_DetectorBase):
     while pending:
       yield finish(pending.popleft())
 
-  def predict_raw(self, frame, pooled=False):
+  def predict_raw(self, frame, pooled=False, mask_rle=False):
     """Decoder-sized frame [H0,W0,3] (uint8 or float32 BGR): the reference's
     ``resizeImage(frame.astype("float32"), short_edge_size, max_size)`` step
     (obj_detect_tracking.py:597-608) runs on the device.  Returns (boxes, labels, probs, feats,
     scale) with boxes in resized-image coordinates, exactly what ``sess.run`` returns after the
-    host-side resize."""
+    host-side resize.  mask_rle=True (add_mask models): one more element, ``masks_rle((H0, W0), scale)``."""
     frame = np.asarray(frame)
     e, scale = self.engine_for_raw(1, frame.shape[0], frame.shape[1])
     boxes, labels, probs, valid, feats, pl = e.forward(frame[None], want_feats=not pooled,
                                                        want_pooled=pooled)
     r = int(valid[0])
-    return (boxes[0, :r].copy(), labels[0, :r].astype(np.int64), probs[0, :r].copy(),
-            pl if pooled else feats, scale)
+    self._last_forward = (e, e.forward_serial())
+    ret = (boxes[0, :r].copy(), labels[0, :r].astype(np.int64), probs[0, :r].copy(),
+           pl if pooled else feats, scale)
+    if mask_rle:
+      ret = ret + (self.masks_rle(frame.shape[:2], scale),)
+    return ret
 
   def _fetch(self, fetches, feed_dict):
     boxes, labels, probs, feats = self.predict(feed_dict[self.image])

@@ -360,3 +360,28 @@ def preprocess_rgb(frames, pad_t, pad_l, Hp, Wp, resize_hw=None, lib=None, devic
   lib.check(lib.dll.odt_op_preprocess_rgb(device, fr.ctypes.data_as(C.c_void_p), dtype, B, Hs, Ws, Hr, Wr, pad_t, pad_l,
                                           Hp, Wp, int(resize_hw is not None), fptr(out)))
   return out
+
+
+def mask_rle(masks, boxes, frame_hw, scale=1.0, want_counts=False, device_ptrs=None, lib=None, device=0):
+  """odt_op_mask_rle: masks [n,28,28] (final_masks) and boxes [n,4] (network coordinates) -> the COCO RLE of each mask
+  pasted into a frame_hw = (H0, W0) frame at boxes / scale, as [{"size": [H0, W0], "counts": str}] (fill_full_mask +
+  pycocotools mask.encode, include/odt.h); want_counts: (rles, [uint32 counts per detection]).  device_ptrs = (masks_ptr,
+  boxes_ptr, n): inputs already on the device (masks / boxes are then ignored)."""
+  lib = _L(lib)
+  res = _lib.OdtRleResult()
+  if device_ptrs is not None:
+    pm, pb, n = device_ptrs
+    keep = None
+    lib.check(lib.dll.odt_op_mask_rle(device, C.c_void_p(pm), C.c_void_p(pb), int(n), 1, int(frame_hw[0]), int(frame_hw[1]),
+                                      float(scale), int(bool(want_counts)), C.byref(res)))
+  else:
+    m = f32(masks).reshape(-1, 28, 28)
+    b = f32(boxes).reshape(-1, 4)
+    assert m.shape[0] == b.shape[0], (m.shape, b.shape)
+    keep = (m, b)
+    lib.check(lib.dll.odt_op_mask_rle(device, m.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), m.shape[0], 0,
+                                      int(frame_hw[0]), int(frame_hw[1]), float(scale), int(bool(want_counts)),
+                                      C.byref(res)))
+  del keep
+  rles = res.rles()
+  return (rles, res.count_lists()) if want_counts else rles
