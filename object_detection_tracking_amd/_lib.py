@@ -8,7 +8,9 @@ e.g. the HIP-on-CPU simulator under tests/emu/, by constructing
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
+import json
 import os
 
 import numpy as np
@@ -231,3 +233,114 @@ def get_lib():
       raise OdtError("libodt_hip.so loaded but no HIP device is visible")
     _LIB = lib
   return _LIB
+
+
+def as_frames(frames):
+  """Host frames as the library reads them -- contiguous, uint8 as it is, anything else as float32 -- and their ODT_DTYPE_*."""
+  fr = np.ascontiguousarray(frames)
+  if fr.dtype == np.uint8:
+    return fr, ODT_DTYPE_U8
+  return np.ascontiguousarray(fr, dtype=np.float32), ODT_DTYPE_F32
+
+
+class _Handle(object):
+  """What the Mask R-CNN engine (models.py) and the EfficientNet / EfficientDet engine (efficientdet/backbone.py) share.
+  Owns ``h``, one handle of ``lib``: odt_create(config: OdtConfig, device), odt_load_tensor for every (name, array) of
+  ``tensors``, odt_finalize_weights.  Every call goes through :meth:`live`: a closed handle raises instead of reaching
+  the library as a null pointer."""
+
+  def __init__(self, lib, config, device, tensors):
+    self.lib = lib
+    self.profiling = False
+    self.h = C.c_void_p()
+    lib.check(lib.dll.odt_create(C.byref(config), device, C.byref(self.h)))
+    try:
+      for name, arr in tensors:
+        a = f32(arr)
+        shape = (C.c_int64 * a.ndim)(*a.shape)
+        lib.check(lib.dll.odt_load_tensor(self.h, name.encode(), fptr(a), C.cast(shape, c_i64_p), a.ndim))
+      lib.check(lib.dll.odt_finalize_weights(self.h))
+    except Exception:
+      self.close()
+      raise
+
+  def close(self):
+    if self.h is not None:
+      self.lib.dll.odt_destroy(self.h)
+      self.h = None
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:
+      pass
+
+  def live(self):
+    """``h``, or OdtError for a closed handle (model.close(), or evicted from the model's plan cache)."""
+    if self.h is None:
+      raise OdtError("engine closed (model.close(), or evicted from the model's plan cache: _DetectorBase.max_engines)")
+    return self.h
+
+  def move(self):
+    """A new wrapper that owns this handle; this one is left closed."""
+    new = copy.copy(self)
+    self.h = None
+    return new
+
+  def set_source_size(self, src_height, src_width):
+    self.lib.check(self.lib.dll.odt_set_source_size(self.live(), int(src_height), int(src_width)))
+
+  def synchronize(self):
+    self.lib.check(self.lib.dll.odt_synchronize(self.live()))
+
+  def describe(self):
+    """What the handle runs (odt_describe): conv arithmetic mode, launches per kernel family, policy thresholds, memory."""
+    buf = C.create_string_buffer(16384)
+    self.lib.check(self.lib.dll.odt_describe(self.live(), buf, 16384))
+    return json.loads(buf.value.decode())
+
+  def tap(self, name):
+    """Stage tensor in the device layout (NHWC; EfficientNet: channel stride padded to 32), as numpy."""
+    h = self.live()
+    shape = (C.c_int64 * 4)(); rank = C.c_int()
+    self.lib.check(self.lib.dll.odt_tap(h, name.encode(), None, 0, C.cast(shape, c_i64_p), C.byref(rank)))
+    out = np.zeros([int(shape[i]) for i in range(rank.value)], np.float32)
+    self.lib.check(self.lib.dll.odt_tap(h, name.encode(), fptr(out), out.size, C.cast(shape, c_i64_p), C.byref(rank)))
+    return out
+
+  def range_health(self, rebase=False):
+    """odt_range_health: the largest growth, over the plan's tensors, of the recorded |max| against the level last accepted
+    (rebase=True accepts the current one), with the producing layer's name -- one or two forwards old, free to read."""
+    f = C.c_double(); amax = C.c_double(); seen = C.c_longlong(); name = C.create_string_buffer(128)
+    self.lib.check(self.lib.dll.odt_range_health(self.live(), int(bool(rebase)), C.byref(f), name, 128, C.byref(amax),
+                                                 C.byref(seen)))
+    return {"worst_growth": f.value, "tensor": name.value.decode(), "tensor_amax": amax.value, "tensors_seen": int(seen.value)}
+
+  def forward_serial(self):
+    """odt_forward_serial: the number of forwards enqueued on this handle (the serial of the most recent one)."""
+    v = C.c_int64()
+    self.lib.check(self.lib.dll.odt_forward_serial(self.live(), C.byref(v)))
+    return int(v.value)
+
+  def profile(self, enable):
+    self.lib.check(self.lib.dll.odt_profile_enable(self.live(), int(enable)))
+    self.profiling = bool(enable)
+
+  def profile_read(self):
+    ms = C.c_double(); fl = C.c_double(); n = C.c_int(); tot = C.c_double()
+    self.lib.check(self.lib.dll.odt_profile_read(self.live(), C.byref(ms), C.byref(fl), C.byref(n), C.byref(tot)))
+    return dict(conv_ms=ms.value, conv_flops=fl.value, conv_launches=n.value, total_ms=tot.value)
+
+  def profile_layers(self):
+    """[(name, flops, ms, (M, N, K))] for every conv launch of the plan."""
+    h = self.live()
+    cnt = C.c_int()
+    self.lib.check(self.lib.dll.odt_profile_layer(h, -1, None, 0, None, None, None, C.byref(cnt)))
+    out = []
+    for i in range(cnt.value):
+      name = C.create_string_buffer(128); fl = C.c_double(); ms = C.c_double()
+      mnk = (C.c_int64 * 3)()
+      self.lib.check(self.lib.dll.odt_profile_layer(h, i, name, 128, C.byref(fl), C.byref(ms), C.cast(mnk, c_i64_p),
+                                                    C.byref(cnt)))
+      out.append((name.value.decode(), fl.value, ms.value, (mnk[0], mnk[1], mnk[2])))
+    return out

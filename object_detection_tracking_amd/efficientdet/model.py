@@ -13,10 +13,13 @@ min(out_w / w, out_h / h), TF-1.x bilinear resize of the normalised image, zero 
 (short_edge_size, max_size)) runs on the device, and the boxes come back multiplied by
 image_scale_to_original like the reference's.
 """
+import collections
+import ctypes as C
+
 import numpy as np
 
 from .. import _lib
-from .._lib import OdtOutputs, fptr, iptr
+from .._lib import OdtOutputs, as_frames, fptr, iptr
 from .arch import NUM_ANCHORS, NUM_CLASSES, det_config, feat_sizes
 from .backbone import EfficientNetBackbone
 
@@ -116,36 +119,35 @@ class EfficientDet(object):
   def predict(self, frame):
     """uint8 (or float32) BGR frame [H0,W0,3] -> (boxes [R,4], labels [R] int32, probs [R],
     fpn_box_feat [R, filters])."""
+    e, fr, dt = self._frame(frame)
+    arrays, out = self._outputs()
+    self.lib.check(self.lib.dll.odt_forward(e.live(), fr.ctypes.data_as(C.c_void_p), dt, 0, None, C.byref(out)))
+    return self._result(arrays)
+
+  def _frame(self, frame, replica=0):
+    """(engine for a frame of this size, the frame as a batch of one, its dtype code)."""
     frame = np.asarray(frame)
-    e = self.engine(frame.shape[:2])
+    return (self.engine(frame.shape[:2], replica=replica),) + as_frames(frame[None])
+
+  def _outputs(self):
+    """Fresh result arrays for one frame, and the OdtOutputs that points at them."""
     per = int(getattr(self.config, "result_per_im", 100))
-    F_ = self.cfg["fpn_num_filters"]
     boxes = np.zeros((1, per, 4), np.float32); probs = np.zeros((1, per), np.float32)
     labels = np.zeros((1, per), np.int32); valid = np.zeros((1,), np.int32)
-    pooled = np.zeros((per, F_), np.float32)
+    pooled = np.zeros((per, self.cfg["fpn_num_filters"]), np.float32)
     out = OdtOutputs()
     out.boxes = fptr(boxes); out.probs = fptr(probs); out.labels = iptr(labels); out.valid = iptr(valid)
     out.feats = None; out.pooled = fptr(pooled); out.masks = None
-    fr = np.ascontiguousarray(frame[None])
-    import ctypes as C
-    from .._lib import ODT_DTYPE_F32, ODT_DTYPE_U8
-    dt = ODT_DTYPE_U8 if fr.dtype == np.uint8 else ODT_DTYPE_F32
-    if dt == ODT_DTYPE_F32:
-      fr = np.ascontiguousarray(fr, np.float32)
-    self.lib.check(self.lib.dll.odt_forward(e.h, fr.ctypes.data_as(C.c_void_p), dt, 0, None, C.byref(out)))
+    return (boxes, labels, probs, valid, pooled), out
+
+  def _result(self, arrays):
+    boxes, labels, probs, valid, pooled = arrays
     r = int(valid[0])
     return boxes[0, :r].copy(), labels[0, :r].copy(), probs[0, :r].copy(), pooled[:r].copy()
 
   def _enqueue(self, frame, replica=0):
-    import ctypes as C
-    from .._lib import ODT_DTYPE_F32, ODT_DTYPE_U8
-    frame = np.asarray(frame)
-    e = self.engine(frame.shape[:2], replica=replica)
-    fr = np.ascontiguousarray(frame[None])
-    dt = ODT_DTYPE_U8 if fr.dtype == np.uint8 else ODT_DTYPE_F32
-    if dt == ODT_DTYPE_F32:
-      fr = np.ascontiguousarray(fr, np.float32)
-    self.lib.check(self.lib.dll.odt_forward_async(e.h, fr.ctypes.data_as(C.c_void_p), dt, 0, None))
+    e, fr, dt = self._frame(frame, replica)
+    self.lib.check(self.lib.dll.odt_forward_async(e.live(), fr.ctypes.data_as(C.c_void_p), dt, 0, None))
     return e, fr                      # (the frame array must outlive the asynchronous H2D copy)
 
   def predict_async(self, frame):
@@ -160,7 +162,6 @@ class EfficientDet(object):
     ~600 dependent launches of ~20 us each, most of them far too small for the chip; frames are independent: 74 -> 98 -> 106
     -> 111 frames/s with one / two / three / four in flight, fewer again beyond -- and four already loses (92) when another
     process holds hardware queues on the same GPU, hence three (profiles/r06_d7_frames_in_flight*.txt, r06_bench_n1.json)."""
-    import collections
     n = max(1, int(in_flight))
     pending = collections.deque()
     for k, frame in enumerate(frames):
@@ -177,18 +178,9 @@ class EfficientDet(object):
     return self._collect(e)
 
   def _collect(self, e):
-    import ctypes as C
-    per = int(getattr(self.config, "result_per_im", 100))
-    F_ = self.cfg["fpn_num_filters"]
-    boxes = np.zeros((1, per, 4), np.float32); probs = np.zeros((1, per), np.float32)
-    labels = np.zeros((1, per), np.int32); valid = np.zeros((1,), np.int32)
-    pooled = np.zeros((per, F_), np.float32)
-    out = OdtOutputs()
-    out.boxes = fptr(boxes); out.probs = fptr(probs); out.labels = iptr(labels); out.valid = iptr(valid)
-    out.feats = None; out.pooled = fptr(pooled); out.masks = None
-    self.lib.check(self.lib.dll.odt_read_outputs(e.h, C.byref(out)))
-    r = int(valid[0])
-    return boxes[0, :r].copy(), labels[0, :r].copy(), probs[0, :r].copy(), pooled[:r].copy()
+    arrays, out = self._outputs()
+    self.lib.check(self.lib.dll.odt_read_outputs(e.live(), C.byref(out)))
+    return self._result(arrays)
 
   def _fetch(self, fetches, feed_dict):
     boxes, labels, probs, feats = self.predict(feed_dict[self.image])

@@ -15,17 +15,22 @@ GPU raises.
 """
 from __future__ import annotations
 
+import collections
+import copy
 import ctypes as C
+import functools
+import itertools
 import os
 
 import numpy as np
 
 from . import _lib
-from ._lib import (ODT_DTYPE_F32, ODT_DTYPE_U8, ODT_GRAPH_MULTI, ODT_GRAPH_SINGLE, OdtConfig,
-                   OdtOutputs, c_i64_p, f32, fptr, iptr)
+from ._lib import (ODT_DTYPE_F32, ODT_DTYPE_U8, ODT_GRAPH_MULTI, ODT_GRAPH_SINGLE, OdtConfig, OdtOutputs, _Handle, as_frames,
+                   fptr, iptr)
 from .anchors import fpn_anchor_fields
 from .config import HEAD_DECODE_CLIP, finalize_config
 from .nn import get_new_hw
+from .range_guard import RangeGuard
 from .frozen_pb import load_frozen_pb
 from .tf_checkpoint import load_checkpoint
 from .weights import expand_class_agnostic_box, load_npz, select_partial_classes
@@ -109,25 +114,16 @@ class _Engine(object):
     arith = getattr(config, "conv_arith", None)
     c.conv_arith = {None: 0, "default": 0, "f32": _lib.ODT_ARITH_F32, "bf16x3": _lib.ODT_ARITH_BF16X3}[arith]
     # conv_split_family: "auto" (the DEFAULT, also for an args object that does not carry the field): start on the fp16x2
-    # kernels, run the first forward(s) on a bf16x3-only twin as well and stay on bf16x3 when the pyramid / RPN tensors of
-    # the two differ by more than f32 rounding level (_auto_calibrate) -- the guard for checkpoints whose activations do
-    # not fit the fp16x2 kernels' per-tensor range (useful content more than 2^17 below a tensor's maximum, DESIGN.md
-    # section 3.1).  Explicit: 0 / 2 the fp16x2 kernels where eligible, unguarded | 3 bf16x3 only | 1 one-stage bf16x3.
+    # kernels under a RangeGuard (range_guard.py).  Explicit: 0 / 2 the fp16x2 kernels where eligible, unguarded | 3 bf16x3
+    # only | 1 one-stage bf16x3.
     fam = getattr(config, "conv_split_family", "auto")
     fam = "auto" if fam is None else fam
-    self._auto = None
     self._family_requested = fam
+    self._guard = None
     if fam == "auto" and c.conv_arith == 0:
-      # (round 6) the guard stays on watch for the whole stream: every forward records its tensors' |max| anyway (the fp16x2
-      # kernels scale by them); when one has grown past `watch_ratio` times the level the last comparison accepted
-      # (odt_range_health) -- a scene cut, an exposure change: an outlier the first frames never showed -- the comparison
-      # against the bf16x3 twin is re-armed for the next forward.  `args` therefore lives as long as the engine (the weights
-      # dict is the model's own).
-      self._auto = {"pending": int(getattr(config, "conv_split_auto_frames", 1) or 1), "chosen": 2, "checks": [],
-                    "tolerance": float(getattr(config, "conv_split_auto_tol", 2e-5)), "deferred": 0, "incomplete": False,
-                    "frames": int(getattr(config, "conv_split_auto_frames", 1) or 1),
-                    "watch_ratio": float(getattr(config, "conv_split_auto_watch_ratio", 8.0)), "rearmed": 0, "watch": None,
-                    "args": (lib, config, graph, batch, height, width, weights, device, num_class)}
+      cfg3 = copy.copy(config)
+      cfg3.conv_split_family = 3
+      self._guard = RangeGuard(config, functools.partial(_Engine, lib, cfg3, graph, batch, height, width, weights, device, num_class))
     if fam == "auto":
       fam = 2
     c.conv_split_family = int(fam)
@@ -135,18 +131,6 @@ class _Engine(object):
     # default plans the activations into an arena (a stage's memory is reused once its consumers have run)
     c.keep_taps = int(bool(getattr(config, "keep_taps", False)))
     c.tail_overlap = -1 if getattr(config, "tail_overlap", True) in (False, -1) else 0      # (False: everything on the compute stream)
-    self.h = C.c_void_p()
-    lib.check(lib.dll.odt_create(C.byref(c), device, C.byref(self.h)))
-    try:
-      for name, arr in weights.items():
-        self._load(name, arr)
-      for i, a in enumerate(fpn_anchor_fields(config)):
-        self._load("anchors/lvl%d" % i, a)
-      lib.check(lib.dll.odt_finalize_weights(self.h))
-    except Exception:
-      lib.dll.odt_destroy(self.h)
-      self.h = None
-      raise
     B, P, Cn = batch, self.per_im, self.channels
     self._boxes = np.zeros((B, P, 4), np.float32)
     self._probs = np.zeros((B, P), np.float32)
@@ -159,50 +143,35 @@ class _Engine(object):
     self._ingest_dtype = ODT_DTYPE_U8
     self._ingest_view = None         # numpy view of the pinned buffer armed by ingest_buffer() (until the next submit)
     self._ingest_views_out = False   # a view into this handle's pinned memory was ever handed out
-    self._retired = []               # handles replaced by the "auto" guard whose pinned memory a caller may still hold
-    self._profile_on = False
+    self._retired = []               # handles replaced by the guard whose pinned memory a caller may still hold
+    anchors = (("anchors/lvl%d" % i, a) for i, a in enumerate(fpn_anchor_fields(config)))
+    self._handle = _Handle(lib, c, device, itertools.chain(weights.items(), anchors))
+
+  # what needs nothing but the handle (_lib._Handle), on the one the engine runs now
+  h = property(lambda self: self._handle.h)      # (None once closed; callers of lib.dll.odt_* read it)
+  tap = property(lambda self: self._handle.tap)
+  forward_serial = property(lambda self: self._handle.forward_serial)
+  profile = property(lambda self: self._handle.profile)
+  profile_read = property(lambda self: self._handle.profile_read)
+  profile_layers = property(lambda self: self._handle.profile_layers)
 
   def set_source_size(self, src_height, src_width):
     """Frames of [B, src_height, src_width, 3] from now on; the bilinear resize to the plan's
     [height, width] (reference resizeImage, nn.py:1540-1560) runs on the device."""
     if (src_height, src_width) != (self.src_height, self.src_width):
-      self.lib.check(self.lib.dll.odt_set_source_size(self.h, int(src_height), int(src_width)))
+      self._handle.set_source_size(src_height, src_width)
       self.src_height, self.src_width = int(src_height), int(src_width)
-      twin = (self._auto or {}).get("twin")
-      if twin is not None:
-        twin.set_source_size(src_height, src_width)
-
-  def _load(self, name, arr):
-    a = f32(arr)
-    shape = (C.c_int64 * a.ndim)(*a.shape)
-    self.lib.check(self.lib.dll.odt_load_tensor(self.h, name.encode(), fptr(a),
-                                                C.cast(shape, c_i64_p), a.ndim))
+      if self._guard is not None and self._guard.twin is not None:
+        self._guard.twin.set_source_size(src_height, src_width)
 
   def close(self):
-    d = object.__getattribute__(self, "__dict__")
-    a = d.get("_auto")
-    if a is not None and "twin" in a:
-      a.pop("twin").close()
-    for h in d.get("_retired", []):
-      self.lib.dll.odt_destroy(h)
-    d["_retired"] = []
-    d["_ingest_view"] = None
-    if self.h is not None:
-      self.lib.dll.odt_destroy(self.h)
-      self.h = None
-
-  def __getattribute__(self, name):
-    # a closed engine (model.close(), or evicted from the model's plan cache) fails loudly instead of passing a null handle
-    if name in ("forward", "submit", "collect", "read_outputs", "forward_device_async", "tap", "set_source_size",
-                "profile", "describe", "forward_serial", "mask_rle") and object.__getattribute__(self, "h") is None:
-      raise _lib.OdtError("engine closed (model.close(), or evicted from the model's plan cache: _DetectorBase.max_engines)")
-    return object.__getattribute__(self, name)
-
-  def __del__(self):
-    try:
-      self.close()
-    except Exception:
-      pass
+    if self._guard is not None:
+      self._guard.close()
+    for old in self._retired:
+      old.close()
+    self._retired = []
+    self._ingest_view = None
+    self._handle.close()
 
   def _outputs(self, want_feats, want_pooled):
     out = OdtOutputs()
@@ -220,133 +189,48 @@ class _Engine(object):
             self._pooled[:total].copy() if want_pooled else None)
 
   def _frames(self, frames):
-    fr = np.ascontiguousarray(frames)
-    if fr.dtype == np.uint8:
-      dt = ODT_DTYPE_U8
-    else:
-      fr = np.ascontiguousarray(fr, dtype=np.float32)
-      dt = ODT_DTYPE_F32
+    fr, dt = as_frames(frames)
     assert fr.shape == (self.batch, self.src_height, self.src_width, 3), fr.shape
-    return fr, dt
+    return fr, fr.ctypes.data_as(C.c_void_p), dt
 
-  # ---- conv_split_family = "auto" --------------------------------------------------------------------------------------
-  AUTO_TAPS = ("p2", "p3", "p4", "p5", "p6", "rpn2", "rpn3", "rpn4", "rpn5", "rpn6")      # (readable after a forward in arena mode too)
+  def _calibrate(self, run):
+    """Ahead of a forward: the guard's comparison of ``run(e)`` on this engine and its twin, when one is due.  Returns
+    True when the engine changed handles."""
+    self._handle.live()              # (a closed engine builds no twin)
+    return self._guard is not None and self._guard.calibrate(self, run)
 
-  def _calibration_due(self):
-    a = self._auto
-    return a is not None and a["pending"] > 0 and a["chosen"] == 2
+  def _forward_blocking(self, src, dt, want_feats=False, want_pooled=False):
+    """odt_forward of host frames at ``src``; the guard's comparisons need the detections only."""
+    out = self._outputs(want_feats, want_pooled)
+    self.lib.check(self.lib.dll.odt_forward(self._handle.live(), src, dt, 0, None, C.byref(out)))
 
-  def _auto_finish(self, incomplete=False):
-    a = self._auto
-    twin = a.pop("twin", None)
-    if twin is not None:
-      twin.close()
-    if a["chosen"] == 3 or incomplete:
-      a.pop("args", None)            # (nothing left to compare: the engine IS the bf16x3 engine, or the guard gave up)
-    if incomplete:
-      a["incomplete"] = True
-      a["pending"] = 0
-
-  def _auto_calibrate(self, run):
-    """One calibration forward: `run(engine)` puts the caller's input through an engine (blocking).  The fp16x2 handle
-    and a bf16x3-only twin (no range assumption at all) see the same input; if any pyramid / RPN tensor differs by more
-    than the tolerance (relative to the tensor's |max|), this engine continues as the twin.  Returns True when the
-    engine changed handles.
-
-    Never while a ticket is outstanding: the blocking forward would overwrite the single device output buffers under
-    the ticket's copy, and a ticket cannot follow the engine to another handle.  Such calls are skipped (counted in
-    describe()); after 16 of them the guard gives up loudly in describe() instead of holding the twin forever."""
-    a = self._auto
-    if not self._calibration_due():
-      return False
-    if self._ticket_want:
-      a["deferred"] += 1
-      if a["deferred"] >= 16:
-        self._auto_finish(incomplete=True)
-      return False
-    import copy
-    lib, config, graph, batch, height, width, weights, device, num_class = a["args"]
-    if "twin" not in a:
-      cfg3 = copy.copy(config)
-      cfg3.conv_split_family = 3
-      a["twin"] = _Engine(lib, cfg3, graph, batch, height, width, weights, device, num_class)
-      if (self.src_height, self.src_width) != (height, width):
-        a["twin"].set_source_size(self.src_height, self.src_width)
-    twin = a["twin"]
-    run(self); run(twin)
-    worst, where = 0.0, None
-    for name in self.AUTO_TAPS:
-      try:
-        x, y = self.tap(name), twin.tap(name)
-      except _lib.OdtError:
-        continue
-      d = float(np.abs(x - y).max() / max(1e-30, float(np.abs(y).max())))
-      if not np.isfinite(d):
-        d = float("inf")
-      if d > worst:
-        worst, where = d, name
-    a["checks"].append({"max_rel_diff": worst, "tensor": where})
-    a["pending"] -= 1
-    swapped = False
-    if worst > a["tolerance"]:
-      # stay on bf16x3: this engine takes over the twin's handle.  State bound to the old handle: no tickets (checked
-      # above); pinned ingest memory a caller may still hold a view of keeps the old handle alive until close();
-      # the profiling switch follows.
-      old = self.h
-      self.h, twin.h = twin.h, None
-      if self._ingest_views_out:
-        self._retired.append(old)
-      else:
-        self.lib.dll.odt_destroy(old)
-      self._ingest_views_out = False
-      if self._profile_on:
-        self.lib.check(self.lib.dll.odt_profile_enable(self.h, 1))
-      a["chosen"] = 3
-      swapped = True
-    if a["chosen"] == 3 or a["pending"] <= 0:
-      self._auto_finish()
-      if a["chosen"] == 2 and a.pop("rebase", False):
-        self.range_health(rebase=True)
-    return swapped
-
-  def range_health(self, rebase=False):
-    """odt_range_health: the largest growth, over the plan's tensors, of the recorded |max| against the level last accepted
-    (rebase=True accepts the current one), with the producing layer's name -- one or two forwards old, free to read."""
-    f = C.c_double(); amax = C.c_double(); seen = C.c_longlong(); name = C.create_string_buffer(128)
-    self.lib.check(self.lib.dll.odt_range_health(self.h, int(bool(rebase)), C.byref(f), name, 128, C.byref(amax), C.byref(seen)))
-    return {"worst_growth": f.value, "tensor": name.value.decode(), "tensor_amax": amax.value, "tensors_seen": int(seen.value)}
+  def take_handle(self, twin):
+    """Continue on ``twin``'s handle, which ``twin`` gives up (the guard's change to bf16x3).  State bound to the old
+    handle: no tickets (the guard never compares with one outstanding); pinned ingest memory a caller may still hold a
+    view of keeps the old handle alive until close(); the profiling switch follows."""
+    old, self._handle = self._handle, twin._handle.move()
+    if self._ingest_views_out:
+      self._retired.append(old)
+    else:
+      old.close()
+    self._ingest_views_out = False
+    if old.profiling:
+      self._handle.profile(True)
 
   def _watch(self):
-    """Continuous half of the "auto" guard: called after every forward / collect / synchronize while the engine runs the
-    fp16x2 kernels."""
-    a = self._auto
-    if a is None or a["chosen"] != 2 or a["pending"] > 0 or a["incomplete"] or "args" not in a:
-      return
-    h = self.range_health()
-    a["watch"] = h
-    if h["worst_growth"] > a["watch_ratio"]:
-      a["pending"] = a["frames"]     # the next forward also runs on a bf16x3 twin (rebuilt: _auto_calibrate)
-      a["rearmed"] += 1
-      a["deferred"] = 0
-      a["rebase"] = True             # a comparison that keeps fp16x2 accepts the new maxima as the level to watch from
+    if self._guard is not None:
+      self._guard.after_forward(self)
+
+  def range_health(self, rebase=False):
+    return self._handle.range_health(rebase)
 
   def forward(self, frames, want_feats=True, want_pooled=False):
     """frames: [B,H,W,3] uint8/float32 BGR host array.  Returns fresh arrays."""
-    fr, dt = self._frames(frames)
-    if self._calibration_due():
-      self._auto_calibrate(lambda e: e.lib.check(e.lib.dll.odt_forward(e.h, fr.ctypes.data_as(C.c_void_p), dt, 0, None,
-                                                                       C.byref(e._outputs(False, False)))))
-    out = self._outputs(want_feats, want_pooled)
-    self.lib.check(self.lib.dll.odt_forward(self.h, fr.ctypes.data_as(C.c_void_p), dt, 0, None,
-                                            C.byref(out)))
+    fr, src, dt = self._frames(frames)
+    self._calibrate(lambda e: e._forward_blocking(src, dt))
+    self._forward_blocking(src, dt, want_feats, want_pooled)
     self._watch()
     return self._result(want_feats, want_pooled)
-
-  def forward_serial(self):
-    """odt_forward_serial: the number of forwards enqueued on this engine's handle (the serial of the most recent one)."""
-    v = C.c_int64()
-    self.lib.check(self.lib.dll.odt_forward_serial(self.h, C.byref(v)))
-    return int(v.value)
 
   def mask_rle(self, frame_hw, scale, serial=None, want_counts=False):
     """odt_mask_rle: the masks of forward ``serial`` (default: the most recent one) as COCO RLE of a frame_hw frame with the
@@ -354,7 +238,7 @@ class _Engine(object):
     obj_detect_tracking.py:715-739).  Raises once another forward has been enqueued since ``serial``."""
     res = _lib.OdtRleResult()
     s = self.forward_serial() if serial is None else int(serial)
-    self.lib.check(self.lib.dll.odt_mask_rle(self.h, s, int(frame_hw[0]), int(frame_hw[1]), float(scale),
+    self.lib.check(self.lib.dll.odt_mask_rle(self._handle.live(), s, int(frame_hw[0]), int(frame_hw[1]), float(scale),
                                              int(bool(want_counts)), C.byref(res)))
     rles = res.rles()
     return (rles, res.count_lists()) if want_counts else rles
@@ -363,7 +247,7 @@ class _Engine(object):
     """The outputs of the most recently enqueued forward (odt_read_outputs): what :meth:`forward` would have
     returned for the frames of the last :meth:`forward_device_async`."""
     out = self._outputs(want_feats, want_pooled)
-    self.lib.check(self.lib.dll.odt_read_outputs(self.h, C.byref(out)))
+    self.lib.check(self.lib.dll.odt_read_outputs(self._handle.live(), C.byref(out)))
     return self._result(want_feats, want_pooled)
 
   def submit(self, frames, want_feats=True, want_pooled=True):
@@ -372,26 +256,19 @@ class _Engine(object):
     asked for crosses PCIe on the way back (the [M,C,7,7] features are 40 MB per 8-frame batch,
     their 7x7 mean 0.8 MB)."""
     if frames is None:                # the frames were written into ingest_buffer(): no staging copy
-      fr, dt = None, self._ingest_dtype
+      src, dt = None, self._ingest_dtype
       view = self._ingest_view        # (None: nothing armed for this ticket -- odt_submit_ex refuses below)
-      if view is not None and self._calibration_due():
-        # the zero-copy path is guarded like the others: both handles read the armed pinned buffer (a blocking forward
-        # does not touch the ingest slots); if the engine moves to the twin's handle, the frames move to ITS buffer
-        src = view.ctypes.data_as(C.c_void_p)
-        if self._auto_calibrate(lambda e: e.lib.check(e.lib.dll.odt_forward(e.h, src, dt, 0, None,
-                                                                            C.byref(e._outputs(False, False))))):
-          keep = view
-          self.ingest_buffer(np.uint8 if dt == ODT_DTYPE_U8 else np.float32)[...] = keep
+      # the zero-copy path is guarded like the others: both handles read the armed pinned buffer (a blocking forward
+      # does not touch the ingest slots); if the engine moves to the twin's handle, the frames move to ITS buffer
+      if view is not None and self._calibrate(lambda e: e._forward_blocking(view.ctypes.data_as(C.c_void_p), dt)):
+        self.ingest_buffer(np.uint8 if dt == ODT_DTYPE_U8 else np.float32)[...] = view
       self._ingest_view = None
     else:
-      fr, dt = self._frames(frames)
-      if self._calibration_due():
-        self._auto_calibrate(lambda e: e.lib.check(e.lib.dll.odt_forward(e.h, fr.ctypes.data_as(C.c_void_p), dt, 0, None,
-                                                                         C.byref(e._outputs(False, False)))))
+      fr, src, dt = self._frames(frames)
+      self._calibrate(lambda e: e._forward_blocking(src, dt))
     t = C.c_int()
     want = (1 if want_feats else 0) | (2 if want_pooled else 0) | (4 if self.add_mask else 0)
-    self.lib.check(self.lib.dll.odt_submit_ex(self.h, fr.ctypes.data_as(C.c_void_p) if fr is not None else None, dt, want,
-                                              C.byref(t)))
+    self.lib.check(self.lib.dll.odt_submit_ex(self._handle.live(), src, dt, want, C.byref(t)))
     self._ticket_want[t.value] = (bool(want_feats), bool(want_pooled))
     return t.value
 
@@ -401,7 +278,7 @@ class _Engine(object):
     ``submit(frames)`` disappears (what 8 co-hosted ranks contend on first is host memory bandwidth)."""
     dt = ODT_DTYPE_U8 if np.dtype(dtype) == np.uint8 else ODT_DTYPE_F32
     buf = C.c_void_p(); nbytes = C.c_size_t()
-    self.lib.check(self.lib.dll.odt_ingest_buffer(self.h, dt, C.byref(buf), C.byref(nbytes)))
+    self.lib.check(self.lib.dll.odt_ingest_buffer(self._handle.live(), dt, C.byref(buf), C.byref(nbytes)))
     self._ingest_dtype = dt
     ctype = C.c_uint8 if dt == ODT_DTYPE_U8 else C.c_float
     n = nbytes.value // C.sizeof(ctype)
@@ -417,7 +294,7 @@ class _Engine(object):
     want_feats = sub[0] if want_feats is None else want_feats
     want_pooled = sub[1] if want_pooled is None else want_pooled
     out = self._outputs(want_feats, want_pooled)
-    self.lib.check(self.lib.dll.odt_collect(self.h, ticket, C.byref(out)))
+    self.lib.check(self.lib.dll.odt_collect(self._handle.live(), ticket, C.byref(out)))
     self._ticket_want.pop(ticket, None)
     self._watch()
     return self._result(want_feats, want_pooled)
@@ -437,36 +314,23 @@ class _Engine(object):
 
   def forward_device_async(self, dev_ptr, dtype, stream=None):
     """Enqueue one forward on frames already resident in HBM (bench path)."""
-    if self._calibration_due():
-      def run(e):
-        e.lib.check(e.lib.dll.odt_forward_async(e.h, C.c_void_p(dev_ptr), dtype, 1, None))
-        e.lib.check(e.lib.dll.odt_synchronize(e.h))
-      self._auto_calibrate(run)
-    self.lib.check(self.lib.dll.odt_forward_async(self.h, C.c_void_p(dev_ptr), dtype, 1,
+    def run(e):
+      e.lib.check(e.lib.dll.odt_forward_async(e._handle.live(), C.c_void_p(dev_ptr), dtype, 1, None))
+      e._handle.synchronize()
+    self._calibrate(run)
+    self.lib.check(self.lib.dll.odt_forward_async(self._handle.live(), C.c_void_p(dev_ptr), dtype, 1,
                                                   C.c_void_p(stream) if stream else None))
 
   def synchronize(self):
-    self.lib.check(self.lib.dll.odt_synchronize(self.h))
+    self._handle.synchronize()
     self._watch()
 
   def describe(self):
-    """What the handle runs (odt_describe): conv arithmetic mode, launches per kernel family, policy thresholds."""
-    import json
-    buf = C.create_string_buffer(16384)
-    self.lib.check(self.lib.dll.odt_describe(self.h, buf, 16384))
-    d = json.loads(buf.value.decode())
-    auto = getattr(self, "_auto", None)      # (EfficientNetBackbone borrows this method: no auto state there)
-    if auto is not None:
-      d["conv_split_family_auto"] = {"chosen": "bf16x3 (family 3)" if auto["chosen"] == 3 else "fp16x2 (family 2)",
-                                     "calibration_forwards_left": max(0, auto["pending"]) if auto["chosen"] == 2 else 0,
-                                     "tolerance": auto["tolerance"], "checks": list(auto["checks"]),
-                                     "calls_skipped_with_tickets_outstanding": auto["deferred"],
-                                     "incomplete": bool(auto["incomplete"]),
-                                     "watch": auto.get("watch"), "watch_ratio": auto.get("watch_ratio"),
-                                     "rearmed": auto.get("rearmed", 0)}
-      d["range_guard"] = ("conv_split_family = \"auto\" (default): fp16x2 kernels checked against a bf16x3-only twin handle on the "
-                          "first forward(s), re-armed whenever a tensor's recorded |max| has grown past watch_ratio times the accepted level (odt_range_health)" + ("; GAVE UP: every call so far had tickets outstanding" if auto["incomplete"] else ""))
-    elif hasattr(self, "_family_requested"):
+    """What the handle runs (odt_describe), and what its range guard has done."""
+    d = self._handle.describe()
+    if self._guard is not None:
+      d["conv_split_family_auto"], d["range_guard"] = self._guard.report()
+    else:
       d["range_guard"] = "off (explicit conv_split_family = %r / conv_arith)" % (self._family_requested,)
     return d
 
@@ -481,41 +345,6 @@ class _Engine(object):
       nz = t > 0
       out[name] = {"amax": amax, "elements": int(t.size),
                    "frac_nonzero_below_2^-17_amax": float(((t < amax * 2.0 ** -17) & nz).sum() / max(1, int(nz.sum())))}
-    return out
-
-  def profile(self, enable):
-    self.lib.check(self.lib.dll.odt_profile_enable(self.h, int(enable)))
-    self._profile_on = bool(enable)
-
-  def profile_read(self):
-    ms = C.c_double(); fl = C.c_double(); n = C.c_int(); tot = C.c_double()
-    self.lib.check(self.lib.dll.odt_profile_read(self.h, C.byref(ms), C.byref(fl), C.byref(n),
-                                                 C.byref(tot)))
-    return dict(conv_ms=ms.value, conv_flops=fl.value, conv_launches=n.value, total_ms=tot.value)
-
-  def profile_layers(self):
-    """[(name, flops, ms, (M, N, K))] for every conv launch of the plan."""
-    cnt = C.c_int()
-    self.lib.check(self.lib.dll.odt_profile_layer(self.h, -1, None, 0, None, None, None,
-                                                  C.byref(cnt)))
-    out = []
-    for i in range(cnt.value):
-      name = C.create_string_buffer(128); fl = C.c_double(); ms = C.c_double()
-      mnk = (C.c_int64 * 3)()
-      self.lib.check(self.lib.dll.odt_profile_layer(self.h, i, name, 128, C.byref(fl), C.byref(ms),
-                                                    C.cast(mnk, c_i64_p), C.byref(cnt)))
-      out.append((name.value.decode(), fl.value, ms.value, (mnk[0], mnk[1], mnk[2])))
-    return out
-
-  def tap(self, name):
-    """Stage tensor in the device layout (NHWC), as numpy."""
-    shape = (C.c_int64 * 4)(); rank = C.c_int()
-    self.lib.check(self.lib.dll.odt_tap(self.h, name.encode(), None, 0, C.cast(shape, c_i64_p),
-                                        C.byref(rank)))
-    dims = [int(shape[i]) for i in range(rank.value)]
-    out = np.zeros(dims, np.float32)
-    self.lib.check(self.lib.dll.odt_tap(self.h, name.encode(), fptr(out), out.size,
-                                        C.cast(shape, c_i64_p), C.byref(rank)))
     return out
 
 
@@ -588,7 +417,6 @@ class _DetectorBase(object):
     cfg_e = self.config
     if stream_set:
       # handles of predict_stream: side by side, no side streams of their own (include/odt.h: tail_overlap)
-      import copy
       key = key + ("stream",)
       cfg_e = copy.copy(self.config); cfg_e.tail_overlap = False
     e = self._engines.pop(key, None)
@@ -633,6 +461,13 @@ class _DetectorBase(object):
     self._engines = {}
 
 
+def _first_image(result, pooled):
+  """A b = 1 engine result as the single-image graph returns it: the valid rows, labels as int64."""
+  boxes, labels, probs, valid, feats, pl = result
+  r = int(valid[0])
+  return boxes[0, :r].copy(), labels[0, :r].astype(np.int64), probs[0, :r].copy(), pl if pooled else feats
+
+
 class Mask_RCNN_FPN(_DetectorBase):
   """b=1 graph (reference models.py:267-973)."""
   graph = ODT_GRAPH_SINGLE
@@ -642,13 +477,10 @@ class Mask_RCNN_FPN(_DetectorBase):
     final_probs [R] f32, fpn_box_feat [R,256,7,7] f32 (or [R,256] if pooled))."""
     img = np.asarray(img)
     e = self.engine(1, img.shape[0], img.shape[1])
-    boxes, labels, probs, valid, feats, pl = e.forward(img[None], want_feats=not pooled,
-                                                       want_pooled=pooled)
-    r = int(valid[0])
-    self.last_masks = e._masks[:r].copy() if e.add_mask else None    # final_masks [R,28,28]
+    ret = _first_image(e.forward(img[None], want_feats=not pooled, want_pooled=pooled), pooled)
+    self.last_masks = e._masks[:len(ret[0])].copy() if e.add_mask else None    # final_masks [R,28,28]
     self._last_forward = (e, e.forward_serial())
-    return (boxes[0, :r].copy(), labels[0, :r].astype(np.int64), probs[0, :r].copy(),
-            pl if pooled else feats)
+    return ret
 
   def masks_rle(self, frame_hw, scale, want_counts=False):
     """The masks of the last ``predict`` / ``predict_raw`` as the reference's JSON holds them: per detection
@@ -670,24 +502,20 @@ class Mask_RCNN_FPN(_DetectorBase):
     (odt_config.tail_overlap = -1) -- 223 / 236 frames/s with three / four in a process that holds no other handles, but 192 / 210
     next to an idle one (streams share hardware queues in creation order: profiles/r06_b1_stream_set.txt); the reference's loop (obj_detect_tracking.py:597-635) sees the same
     per-frame results, one frame later.  Yields what ``predict`` returns."""
-    import collections
     n = max(1, int(in_flight))
     pending = collections.deque()
 
-    def finish(item):
-      e, t = item
-      boxes, labels, probs, valid, feats, pl = e.collect(t)
-      r = int(valid[0])
-      return (boxes[0, :r].copy(), labels[0, :r].astype(np.int64), probs[0, :r].copy(), pl if pooled else feats)
+    def finish(e, ticket):
+      return _first_image(e.collect(ticket), pooled)
 
     for k, img in enumerate(frames):
       img = np.asarray(img)
       if len(pending) == n:
-        yield finish(pending.popleft())
+        yield finish(*pending.popleft())
       e = self.engine(1, img.shape[0], img.shape[1], replica=k % n, stream_set=n > 2)
       pending.append((e, e.submit(img[None], want_feats=not pooled, want_pooled=pooled)))
     while pending:
-      yield finish(pending.popleft())
+      yield finish(*pending.popleft())
 
   def predict_raw(self, frame, pooled=False, mask_rle=False):
     """Decoder-sized frame [H0,W0,3] (uint8 or float32 BGR): the reference's
@@ -697,12 +525,8 @@ class Mask_RCNN_FPN(_DetectorBase):
     host-side resize.  mask_rle=True (add_mask models): one more element, ``masks_rle((H0, W0), scale)``."""
     frame = np.asarray(frame)
     e, scale = self.engine_for_raw(1, frame.shape[0], frame.shape[1])
-    boxes, labels, probs, valid, feats, pl = e.forward(frame[None], want_feats=not pooled,
-                                                       want_pooled=pooled)
-    r = int(valid[0])
+    ret = _first_image(e.forward(frame[None], want_feats=not pooled, want_pooled=pooled), pooled) + (scale,)
     self._last_forward = (e, e.forward_serial())
-    ret = (boxes[0, :r].copy(), labels[0, :r].astype(np.int64), probs[0, :r].copy(),
-           pl if pooled else feats, scale)
     if mask_rle:
       ret = ret + (self.masks_rle(frame.shape[:2], scale),)
     return ret

@@ -11,7 +11,7 @@ _W = {}
 
 def make_config(**kw):
   """The package's make_config with conv_split_family pinned to 0 (the fp16x2 kernels where eligible, UNGUARDED) unless
-  the test says otherwise: the product default is "auto" (a bf16x3 twin handle checks the first forward, models._Engine),
+  the test says otherwise: the product default is "auto" (a bf16x3 twin handle checks the first forward, range_guard.RangeGuard),
   which would build two handles and run two extra forwards in every test.  The guard and the default itself have their own
   tests (test_e2e.py: test_auto_family_*, test_default_engine_is_guarded, test_trained_like_bn_statistics_*)."""
   kw.setdefault("conv_split_family", 0)

@@ -308,6 +308,18 @@ def test_frozen_model_named_tensor_contract(emu_lib, tmp_path):
     mm.close()
 
 
+def test_closed_engine_never_reaches_the_library(emu_lib):
+  """Every engine call that hands the handle to the library raises on a closed engine, also the ones that take no frames."""
+  cfg = small_config(resnet_num_block=[1, 1, 1, 1], rpn_test_post_nms_topk=16)
+  m = models.get_model(cfg, 0, weights=weights_for(cfg), lib=emu_lib)
+  e = m.engine(1, 64, 96)
+  m.close()
+  assert e.h is None
+  for call in (e.synchronize, e.range_health, e.profile_read, e.profile_layers, e.ingest_buffer):
+    with pytest.raises(OdtError, match="engine closed"):
+      call()
+
+
 def test_engine_cache_is_bounded(emu_lib):
   """Frames of ever-changing sizes must not accumulate static plans (each owns activations + a weight copy)."""
   cfg = small_config(resnet_num_block=[1, 1, 1, 1], rpn_test_post_nms_topk=16)

@@ -771,8 +771,8 @@ def test_default_engine_is_guarded_on_every_entry_path(backend, monkeypatch):
           assert np.array_equal(view, fr)             # the caller's view is still readable memory, whatever the guard chose
         auto = e.describe()["conv_split_family_auto"]
         assert len(auto["checks"]) == 1 and auto["calibration_forwards_left"] == 0 and not auto["incomplete"], auto
-        assert "twin" not in e._auto                                      # the twin handle is released (the weights dict is the model's own:
-        assert ("args" in e._auto) == (kind == "ordinary")                # kept while the guard watches an fp16x2 engine)
+        assert e._guard.twin is None                                      # the twin handle is released (the weights dict is the model's own:
+        assert (e._guard.make_twin is not None) == (kind == "ordinary")   # kept while the guard watches an fp16x2 engine)
         assert e.profile_read()["conv_launches"] > 0                      # profiling survived a handle change
         if kind == "ordinary":
           assert auto["chosen"].startswith("fp16x2"), auto
@@ -802,7 +802,7 @@ def test_default_engine_is_guarded_on_every_entry_path(backend, monkeypatch):
     assert np.array_equal(r0[0], r1[0])
     e.forward(fr)                                                         # nothing outstanding: the second check runs
     a = e.describe()["conv_split_family_auto"]
-    assert len(a["checks"]) == 2 and a["calibration_forwards_left"] == 0 and "twin" not in e._auto, a
+    assert len(a["checks"]) == 2 and a["calibration_forwards_left"] == 0 and e._guard.twin is None, a
   finally:
     m.close()
 
@@ -1085,7 +1085,7 @@ def test_continuous_range_guard_host_logic(emu_lib, monkeypatch):
     h = e.range_health()
     assert set(h) == {"worst_growth", "tensor", "tensor_amax", "tensors_seen"} and h["worst_growth"] <= 1.0, h   # (exact-f32 plan at this size: the preprocessed frames' record at most)
     a = e.describe()["conv_split_family_auto"]
-    assert a["chosen"].startswith("fp16x2") and len(a["checks"]) == 1 and a["rearmed"] == 0 and "twin" not in e._auto and "args" in e._auto, a
+    assert a["chosen"].startswith("fp16x2") and len(a["checks"]) == 1 and a["rearmed"] == 0 and e._guard.twin is None and e._guard.make_twin is not None, a
     state = {"growth": 1000.0, "rebased": 0}
     def fake(self, rebase=False):
       out = {"worst_growth": state["growth"], "tensor": "pool0", "tensor_amax": 1e9, "tensors_seen": 7}
@@ -1099,7 +1099,7 @@ def test_continuous_range_guard_host_logic(emu_lib, monkeypatch):
     e.forward(fr, want_feats=False, want_pooled=True)             # ... this one runs on a fresh twin as well
     a = e.describe()["conv_split_family_auto"]
     assert len(a["checks"]) == 2 and a["calibration_forwards_left"] == 0 and a["chosen"].startswith("fp16x2"), a
-    assert state["rebased"] == 1 and "twin" not in e._auto        # fp16x2 kept: the new maxima are the level to watch from
+    assert state["rebased"] == 1 and e._guard.twin is None        # fp16x2 kept: the new maxima are the level to watch from
     e.forward(fr, want_feats=False, want_pooled=True)             # same maxima again: growth 1, no re-arm
     assert e.describe()["conv_split_family_auto"]["rearmed"] == 1
   finally:

@@ -63,12 +63,11 @@ def effdet(a):
   fr = synthetic_frames(1, S, S)[0]
   e = m.engine((S, S))
   m.predict(fr)
-  E = models._Engine                     # (the profiling entry points only need .lib and .h)
-  E.profile(e, True)
+  e.profile(True)
   for _ in range(a.steps):
     m.predict(fr)
-  rows = E.profile_layers(e)
-  tot = E.profile_read(e)
+  rows = e.profile_layers()
+  tot = e.profile_read()
   groups = collections.OrderedDict()
   for name, fl, ms, mnk in rows:
     if "[fused into" in name:
