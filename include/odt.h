@@ -374,6 +374,17 @@ int odt_op_bottleneck_tail(int device, const float* in, int B, int H, int W, int
  * (Wq alike).  grid > 0: that many workgroups (tests: several tiles per persistent workgroup). */
 int odt_op_stem(int device, const float* frame_pad, int B, int Hp, int Wp, const float* w_hwio, const float* bias,
                 int fuse, int grid, float* out);
+/* Which conv kernel would run this layer -- the library's selection (conv_select), reported; touches no device, so it runs
+ * on a host without a GPU.  shape[ODT_CONV_CHOICE_SHAPE]: B, H, W, Cin, Cout, kh, kw, stride, dil, pad, Ho, Wo, in_Wa (row
+ * pitch of the input in pixels), Cin2 (second K-concatenated source, 0: none), res_mode, ranges (1: the source tensors come
+ * with a recorded |max|), in_ldc, out_ldc (0: dense).  conv_arith / conv_split_family: as in odt_config; the ODT_* knobs
+ * are read at the call.  out[ODT_CONV_CHOICE_OUT]: status (0 exact f32 | 1 split kernels | 2 the record is rejected,
+ * odt_last_error says why), family (1 one-stage bf16x3 | 2 fp16x2 | 3 8-wave bf16x3), bm, bn, kw-reuse, splitk,
+ * double-stage | exact f32: tile (1 128x64 | 2 64x64 | 3 128x128), LDS stages, fine-grained loop | reduce_blocks.
+ * name: the row of the kernel table (may be NULL). */
+#define ODT_CONV_CHOICE_SHAPE 18
+#define ODT_CONV_CHOICE_OUT 11
+int odt_op_conv_choice(const int* shape, int conv_arith, int conv_split_family, int* out, char* name, int name_cap);
 /* image preprocess (models.py:340-355) + zero pad -> [B,Hp,Wp,4] */
 int odt_op_preprocess(int device, const void* frames, int dtype, int B, int H,
                       int W, int pad_t, int pad_l, int Hp, int Wp, float* out);

@@ -416,7 +416,7 @@ const float* conv_h2_chinv(const void* img, int Cout, int K) {
 
 int conv_make_h2_weights(const ConvParams& p, void* img_dev, hipStream_t stream) {
   const int K = p.kh * p.kw * p.Cin + (p.in2 != nullptr ? p.Cin2 : 0);
-  const int bn = p.wt_split_bn;
+  const int bn = conv_variant_row(p.variant).bn;
   ODT_CHECK((bn == 256 || bn == 128 || bn == 64) && p.Cin % 32 == 0 && (p.in2 == nullptr || p.Cin2 % 32 == 0) && cout_padded(p.Cout) % bn == 0,
             "conv_make_h2_weights: 256- / 128- / 64-wide n-tiles and 32-channel slices required");
   float* chinv = const_cast<float*>(conv_h2_chinv(img_dev, p.Cout, K));
@@ -447,8 +447,9 @@ int conv_make_h2f_weights(const float* wt, int Cout, int K, void* img_dev, hipSt
 // 256-wide (res4), 128-wide (res3) or 64-wide (res2) n-tiles = its whole Cout, plain dense output, ReLU or none; b: dense same-size 1x1, single source,
 // no residual or a same-shape one, on the fp16x2 family as well (so its consumers find a recorded range)
 bool conv_h2f_fusable(const ConvParams& a, const ConvParams& b) {
-  const bool a_ok = a.wt_split != nullptr && a.wt_split_kind == 2 && a.wt_split_kwr == 1 && a.wt_split_bm == 256 &&
-                    a.wt_split_bn == a.Cout && (a.Cout == 256 || a.Cout == 128 || a.Cout == 64) && a.splitk <= 1 && a.head_wt == nullptr &&
+  // (a 64-wide conv2 on the kw-reuse kernel's 512 x 64 tiles: the fused tail works on 256-row tiles -- same weight image)
+  const ConvKernelRow& fa = conv_variant_row(conv_variant_fused_tail(a.variant));
+  const bool a_ok = a.wt_split != nullptr && fa.launch != nullptr && fa.bn == a.Cout && a.splitk <= 1 && a.head_wt == nullptr &&
                     a.res_mode == 0 && a.in2 == nullptr && a.relu <= 1 && a.nlvl <= 1 && a.out_oy == 0 && a.out_ox == 0 &&
                     a.out_H == a.Ho && a.out_W == a.Wo && a.f_wt == nullptr;
   const bool b_ok = b.in == a.out && b.kh == 1 && b.kw == 1 && b.stride == 1 && b.pad_t == 0 && b.pad_l == 0 && b.Cin == a.Cout &&
@@ -456,7 +457,7 @@ bool conv_h2f_fusable(const ConvParams& a, const ConvParams& b) {
                     b.Wo == a.Wo && b.in_Ha == a.out_H && b.in_Wa == a.out_W && b.Cout % 32 == 0 && b.out_oy == 0 && b.out_ox == 0 &&
                     b.out_H == b.Ho && b.out_W == b.Wo && b.out_ldc % 4 == 0 && b.out_ldc >= b.Cout &&
                     (b.res_mode == 0 || (b.res_mode == 1 && b.res_H == b.Ho && b.res_W == b.Wo && b.res_ldc % 4 == 0)) &&
-                    b.relu <= 1 && b.nlvl <= 1 && b.head_wt == nullptr && b.splitk <= 1 && b.wt_split != nullptr && b.wt_split_kind == 2 &&
+                    b.relu <= 1 && b.nlvl <= 1 && b.head_wt == nullptr && b.splitk <= 1 && b.wt_split != nullptr && conv_variant_row(b.variant).family == CF_H2 &&
                     b.f_wt == nullptr && (double)b.B * b.Ho * b.Wo * b.out_ldc * 4.0 < 2147483648.0;
   return a_ok && b_ok;
 }
@@ -468,38 +469,16 @@ int launch_tensor_amax(const float* x, size_t n, unsigned* slot, hipStream_t str
   return 0;
 }
 
-int launch_conv_h2(const ConvParams& p, const ConvParams* dev, hipStream_t stream) {
-  if (p.stem_pool) return launch_conv_stem(p, dev, stream);
-  const long M = (long)p.B * p.Ho * p.Wo;
-  const int bn = p.wt_split_bn;
-  const int bm = p.wt_split_bm;
-  const int sk = p.splitk > 1 ? p.splitk : 1;
-  const unsigned grid = (unsigned)(((M + bm - 1) / bm) * (cout_padded(p.Cout) / bn) * sk);
-  if (p.wt_split_kwr) {
-    launch_conv_h2k(p, dev, grid, stream);
-  } else if (bm == 64 && p.h2_bk64) {
-    // the dense 1x1 reductions on two-wave tiles: double stages (conv_h2d.hip; ODT_CONV_H2_BK64=0: the single-stage kernel, A/B)
-    launch_conv_h2d(p, dev, grid, stream);
-  } else if (bm == 64 && bn == 64) {         // ... 64 x 64 tiles: twice the workgroups again (latency-bound reductions at b = 1)
-    hipLaunchKernelGGL((conv_h2_kernel<1, 1, false>), dim3(grid), dim3(128), 0, stream, dev);
-  } else if (bm == 64) {                     // few-row layers (b = 1 below res3): 64 x 128 tiles on two waves, three workgroups per CU, no split-K
-    hipLaunchKernelGGL((conv_h2_kernel<2, 1, false>), dim3(grid), dim3(128), 0, stream, dev);
-  } else if (bn == 64 && bm == 512) {
-    hipLaunchKernelGGL((conv_h2_kernel<2, 8, false, 1>), dim3(grid), dim3(512), 0, stream, dev);
-  } else if (bn == 64) {
-    hipLaunchKernelGGL((conv_h2_kernel<1, 2, false>), dim3(grid), dim3(256), 0, stream, dev);
-  } else if (bn == 256) {
-    if (p.trace != nullptr) hipLaunchKernelGGL((conv_h2_kernel<4, 4, true>), dim3(grid), dim3(512), 0, stream, dev);
-    else hipLaunchKernelGGL((conv_h2_kernel<4, 4, false>), dim3(grid), dim3(512), 0, stream, dev);
-  } else if (bm == 256) {
-    hipLaunchKernelGGL((conv_h2_kernel<2, 4, false>), dim3(grid), dim3(512), 0, stream, dev);
-  } else {
-    if (p.trace != nullptr) hipLaunchKernelGGL((conv_h2_kernel<2, 2, true>), dim3(grid), dim3(256), 0, stream, dev);
-    else hipLaunchKernelGGL((conv_h2_kernel<2, 2, false>), dim3(grid), dim3(256), 0, stream, dev);
-  }
-  if (sk > 1) launch_split_reduce(p, dev, stream);
-  ODT_HIP(hipGetLastError());
-  return 0;
+void conv_rows_h2(ConvKernelRow* t) {      // <TN, WM, TRACE, WN = 2>: WM x WN waves, tile WM * 64 x WN * TN * 32
+  // 64 x 64 tiles: twice the workgroups again (latency-bound reductions at b = 1)
+  ODT_CONV_ROW(t, H2_64x64, CF_H2, 64, 64, 128, 0, (conv_h2_kernel<1, 1, false>));
+  // few-row layers (b = 1 below res3): 64 x 128 tiles on two waves, three workgroups per CU, no split-K
+  ODT_CONV_ROW(t, H2_64x128, CF_H2, 64, 128, 128, 0, (conv_h2_kernel<2, 1, false>));
+  ODT_CONV_ROW(t, H2_512x64, CF_H2, 512, 64, 512, 0, (conv_h2_kernel<2, 8, false, 1>));
+  ODT_CONV_ROW(t, H2_128x64, CF_H2, 128, 64, 256, 0, (conv_h2_kernel<1, 2, false>));
+  ODT_CONV_ROW_T(t, H2_256x256, CF_H2, 256, 256, 512, 0, (conv_h2_kernel<4, 4, false>), (conv_h2_kernel<4, 4, true>));
+  ODT_CONV_ROW(t, H2_256x128, CF_H2, 256, 128, 512, 0, (conv_h2_kernel<2, 4, false>));
+  ODT_CONV_ROW_T(t, H2_128x128, CF_H2, 128, 128, 256, 0, (conv_h2_kernel<2, 2, false>), (conv_h2_kernel<2, 2, true>));
 }
 
 }  // namespace odt

@@ -9,7 +9,7 @@
 // another (per tile fixed) order, i.e. results equal at f32 rounding level, deterministic run to run.
 // ("d" for double stage -- not round 3's archived conv_h2d_kernel.inc experiment, which put the activations on the LDS-DMA path.)
 // Scope: 1x1, stride 1, dense input rows, one source, no split-K, an even number of 32-channel slices; everything else
-// stays on conv_h2_kernel (launch_conv_h2 decides).  Reference ops: as conv_split.hip (nn.py:337-381, :503-521).
+// stays on conv_h2_kernel (conv_select decides).  Reference ops: as conv_split.hip (nn.py:337-381, :503-521).
 #include "conv_split_epilogue.hpp"
 
 namespace odt {
@@ -215,16 +215,16 @@ __global__ void __launch_bounds__(128, 2) conv_h2d_kernel(const ConvParams* __re
 
 }  // namespace
 
+// the dense 1x1 reductions on two-wave tiles (the H2_64x64 / H2_64x128 rows' layers): same-size, single source, at least two
+// double stages.  (A traced record keeps the single-stage kernel.)
 bool conv_h2d_fits(const ConvParams& p) {
-  const int bn = p.wt_split_bn;
-  return p.wt_split_kind == 2 && p.wt_split_bm == 64 && (bn == 64 || bn == 128) && !p.wt_split_kwr && p.kh == 1 && p.kw == 1 &&
-         p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.H == p.in_Ha && p.W == p.in_Wa && p.Ho == p.H && p.Wo == p.W &&
-         p.in2 == nullptr && p.splitk <= 1 && p.f_wt == nullptr && p.nlvl <= 1 && p.trace == nullptr && p.Cin % 64 == 0 && p.Cin >= 128;
+  return p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.H == p.in_Ha && p.W == p.in_Wa && p.Ho == p.H &&
+         p.Wo == p.W && p.in2 == nullptr && p.f_wt == nullptr && p.nlvl <= 1 && p.trace == nullptr && p.Cin % 64 == 0 && p.Cin >= 128;
 }
 
-void launch_conv_h2d(const ConvParams& p, const ConvParams* dev, unsigned grid, hipStream_t stream) {
-  if (p.wt_split_bn == 64) hipLaunchKernelGGL((conv_h2d_kernel<1>), dim3(grid), dim3(128), 0, stream, dev);
-  else hipLaunchKernelGGL((conv_h2d_kernel<2>), dim3(grid), dim3(128), 0, stream, dev);
+void conv_rows_h2d(ConvKernelRow* t) {
+  ODT_CONV_ROW(t, H2D_64x64, CF_H2, 64, 64, 128, CVF_DSTAGE, (conv_h2d_kernel<1>));
+  ODT_CONV_ROW(t, H2D_64x128, CF_H2, 64, 128, 128, CVF_DSTAGE, (conv_h2d_kernel<2>));
 }
 
 }  // namespace odt

@@ -467,7 +467,7 @@ __global__ void __launch_bounds__(512, 2) conv_h2k_kernel(const ConvParams* __re
                          : (f32x4)__builtin_amdgcn_raw_buffer_load_b128(rs_bias, q * 16, 0, 0);
       *reinterpret_cast<f32x4*>(lds + G::F_KOFF + (tid >> 6) * 1024 + q * 16) = v;
     }
-    {   // ... and the fused conv's: [0] 2^-t_n, [1] bias_n (f_cout <= 1024: launch_conv_h2)
+    {   // ... and the fused conv's: [0] 2^-t_n, [1] bias_n (f_cout <= 1024: conv_check_variant)
       const int q = tid & 255;
       const __amdgpu_buffer_rsrc_t rs_k3 = __builtin_amdgcn_make_buffer_rsrc((void*)(tid < 256 ? p.f_chinv : p.f_bias), 0, (int)((unsigned)p.f_cout * 4u), 0x00020000);
       const f32x4 v = (f32x4)__builtin_amdgcn_raw_buffer_load_b128(rs_k3, q * 16, 0, 0);
@@ -597,23 +597,14 @@ __global__ void __launch_bounds__(512, 2) conv_h2k_kernel(const ConvParams* __re
 
 }  // namespace
 
-void launch_conv_h2k(const ConvParams& p, const ConvParams* dev, unsigned grid, hipStream_t stream) {
-  const int bn = p.wt_split_bn;
-  if (p.f_wt != nullptr) {                   // fused 1x1 tail (launch_conv_h2 checked the shape)
-    if (bn == 64) hipLaunchKernelGGL((conv_h2k_kernel<1, false, true>), dim3(grid), dim3(512), 0, stream, dev);
-    else if (bn == 128) hipLaunchKernelGGL((conv_h2k_kernel<2, false, true>), dim3(grid), dim3(512), 0, stream, dev);
-    else if (p.trace != nullptr) hipLaunchKernelGGL((conv_h2k_kernel<4, true, true>), dim3(grid), dim3(512), 0, stream, dev);
-    else hipLaunchKernelGGL((conv_h2k_kernel<4, false, true>), dim3(grid), dim3(512), 0, stream, dev);
-  } else if (bn == 256) {
-    if (p.trace != nullptr) hipLaunchKernelGGL((conv_h2k_kernel<4, true>), dim3(grid), dim3(512), 0, stream, dev);
-    else hipLaunchKernelGGL((conv_h2k_kernel<4, false>), dim3(grid), dim3(512), 0, stream, dev);
-  } else if (bn == 128) {
-    hipLaunchKernelGGL((conv_h2k_kernel<2, false>), dim3(grid), dim3(512), 0, stream, dev);
-  } else if (p.wt_split_bm == 512) {          // 64-wide layer, eight waves stacked along M: 512 x 64 tiles
-    hipLaunchKernelGGL((conv_h2k_kernel<2, false, false, 1>), dim3(grid), dim3(512), 0, stream, dev);
-  } else {
-    hipLaunchKernelGGL((conv_h2k_kernel<1, false>), dim3(grid), dim3(512), 0, stream, dev);
-  }
+void conv_rows_h2k(ConvKernelRow* t) {     // <TN, TRACE, FUSE, WN = 2>: 8 waves, tile 256 x TN * 64 (WN = 1: stacked along M, 512 x 64)
+  ODT_CONV_ROW(t, H2KF_256x64, CF_H2, 256, 64, 512, CVF_KWR | CVF_FTAIL, (conv_h2k_kernel<1, false, true>));
+  ODT_CONV_ROW(t, H2KF_256x128, CF_H2, 256, 128, 512, CVF_KWR | CVF_FTAIL, (conv_h2k_kernel<2, false, true>));
+  ODT_CONV_ROW_T(t, H2KF_256x256, CF_H2, 256, 256, 512, CVF_KWR | CVF_FTAIL, (conv_h2k_kernel<4, false, true>), (conv_h2k_kernel<4, true, true>));
+  ODT_CONV_ROW_T(t, H2K_256x256, CF_H2, 256, 256, 512, CVF_KWR, (conv_h2k_kernel<4, false>), (conv_h2k_kernel<4, true>));
+  ODT_CONV_ROW(t, H2K_256x128, CF_H2, 256, 128, 512, CVF_KWR, (conv_h2k_kernel<2, false>));
+  ODT_CONV_ROW(t, H2K_512x64, CF_H2, 512, 64, 512, CVF_KWR, (conv_h2k_kernel<2, false, false, 1>));      // 64-wide layer, eight waves stacked along M
+  ODT_CONV_ROW(t, H2K_256x64, CF_H2, 256, 64, 512, CVF_KWR, (conv_h2k_kernel<1, false>));
 }
 
 }  // namespace odt

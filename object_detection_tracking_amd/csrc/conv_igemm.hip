@@ -587,15 +587,22 @@ __global__ void __launch_bounds__(256, ST == 1 ? 3 : 2) conv_igemm_kernel(const 
   stamp(5);
 }
 
-template <int WM, int WN, int TM, int TN, int ST, bool FINE>
-void launch_variant(const ConvParams& p, const ConvParams* dev, hipStream_t stream) {
-  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-  const int M = p.B * p.Ho * p.Wo;
-  const unsigned grid = (unsigned)(((M + BM - 1) / BM) * ((p.Cout + BN - 1) / BN));
-  hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, ST, FINE>), dim3(grid), dim3(256), 0, stream, dev);
-}
-
 }  // namespace
+
+void conv_rows_f32(ConvKernelRow* t) {       // <WM, WN, TM, TN, ST, FINE>: 4 waves, tile WM * TM * 32 x WN * TN * 32
+  ODT_CONV_ROW(t, F32_128x64_S1_FINE, CF_F32, 128, 64, 256, CVF_FINE, (conv_igemm_kernel<4, 1, 1, 2, 1, true>));
+  ODT_CONV_ROW(t, F32_128x64_S1, CF_F32, 128, 64, 256, 0, (conv_igemm_kernel<4, 1, 1, 2, 1, false>));
+  ODT_CONV_ROW(t, F32_64x64_S1_FINE, CF_F32, 64, 64, 256, CVF_FINE, (conv_igemm_kernel<2, 2, 1, 1, 1, true>));      // 64 x 64: fill the 256 CUs on small M
+  ODT_CONV_ROW(t, F32_64x64_S1, CF_F32, 64, 64, 256, 0, (conv_igemm_kernel<2, 2, 1, 1, 1, false>));
+  ODT_CONV_ROW(t, F32_128x128_S1_FINE, CF_F32, 128, 128, 256, CVF_FINE, (conv_igemm_kernel<2, 2, 2, 2, 1, true>));
+  ODT_CONV_ROW(t, F32_128x128_S1, CF_F32, 128, 128, 256, 0, (conv_igemm_kernel<2, 2, 2, 2, 1, false>));
+  ODT_CONV_ROW(t, F32_128x64_S2_FINE, CF_F32, 128, 64, 256, CVF_ST2 | CVF_FINE, (conv_igemm_kernel<4, 1, 1, 2, 2, true>));
+  ODT_CONV_ROW(t, F32_128x64_S2, CF_F32, 128, 64, 256, CVF_ST2, (conv_igemm_kernel<4, 1, 1, 2, 2, false>));
+  ODT_CONV_ROW(t, F32_64x64_S2_FINE, CF_F32, 64, 64, 256, CVF_ST2 | CVF_FINE, (conv_igemm_kernel<2, 2, 1, 1, 2, true>));
+  ODT_CONV_ROW(t, F32_64x64_S2, CF_F32, 64, 64, 256, CVF_ST2, (conv_igemm_kernel<2, 2, 1, 1, 2, false>));
+  ODT_CONV_ROW(t, F32_128x128_S2_FINE, CF_F32, 128, 128, 256, CVF_ST2 | CVF_FINE, (conv_igemm_kernel<2, 2, 2, 2, 2, true>));
+  ODT_CONV_ROW(t, F32_128x128_S2, CF_F32, 128, 128, 256, CVF_ST2, (conv_igemm_kernel<2, 2, 2, 2, 2, false>));
+}
 
 static void make_div(unsigned d, unsigned* mul, unsigned* sh) {
   if (d <= 1) { *mul = 0; *sh = 0; return; }
@@ -633,106 +640,7 @@ int conv_check(const ConvParams& p) {
   ODT_CHECK((double)p.B * p.out_H * p.out_W * p.out_ldc * 4.0 < 2147483648.0 &&
             (p.res_mode == 0 || (double)p.B * p.res_H * p.res_W * p.res_ldc * 4.0 < 2147483648.0),
             "conv: output / residual tensors must be smaller than 2 GiB (32-bit buffer offsets)");
-  ODT_CHECK(p.nlvl <= 1 || (p.wt_split != nullptr && p.wt_split_kind == 3 && p.splitk <= 1 && p.nlvl <= 5 && p.head_wt == nullptr),
-            "conv: per-row-range epilogue constants need a conv_split3 kernel without split-K");
-  if (p.wt_split == nullptr) return 0;
-  // the split kernel families (launch_conv_split)
-  const long M = (long)p.B * p.Ho * p.Wo;
-  const int bm = p.wt_split_bm, sk = p.splitk > 1 ? p.splitk : 1;
-  ODT_CHECK(sk == 1 || p.reduce_blocks > 0, "conv: split-K without a combine-pass grid");
-  if (p.wt_split_kind == 2 && p.stem_pool) {
-    ODT_CHECK(conv_stem_fits(p) && p.out != nullptr && p.out_H == (p.Ho + 1 - 3) / 2 + 1 && p.out_W == (p.Wo + 1 - 3) / 2 + 1 &&
-              p.out_oy == 0 && p.out_ox == 0, "conv stem: unsupported shape");
-  } else if (p.wt_split_kind == 2) {
-    const int bn = p.wt_split_bn;
-    ODT_CHECK(((bm == 256 && (bn >= 128 || p.wt_split_kwr)) || (bm == 128 && bn <= 128 && !p.wt_split_kwr) ||
-               (bm == 512 && bn == 64 && (!p.wt_split_kwr || p.Ho * p.Wo >= 512)) || (bm == 64 && (bn == 128 || bn == 64) && !p.wt_split_kwr)) && (bn == 256 || bn == 128 || bn == 64) && p.Cin % 32 == 0 && p.kh * p.kw <= 32 && p.in_amax != nullptr &&
-              p.h2_chinv != nullptr && (p.in2 == nullptr || (p.in2_amax != nullptr && p.Cin2 % 32 == 0)) && p.nlvl <= 1,
-              "conv h2: unsupported tile / shape, or no recorded input range");
-    ODT_CHECK(sk == 1 || (p.partial != nullptr && p.in2 == nullptr && p.head_wt == nullptr && (p.kh * p.kw * p.Cin >> 5) >= sk),
-              "conv h2: split-K needs a partial buffer, a single source and at least one stage per range");
-    ODT_CHECK(p.f_wt == nullptr || p.wt_split_kwr, "conv h2: a fused 1x1 tail needs the kw-reuse kernel");
-    if (p.wt_split_kwr) {
-      ODT_CHECK(p.kw == 3 && p.stride == 1 && p.in_Wa == p.Wo && p.in2 == nullptr && 2 * p.dil <= 4 &&
-                (sk == 1 || (bm == 256 && bn >= 128 && p.f_wt == nullptr && p.kh * (p.Cin >> 5) >= sk)), "conv h2k: unsupported shape");
-      ODT_CHECK(p.f_wt == nullptr || (bm == 256 && bn == p.Cout && (bn == 256 || bn == 128 || bn == 64) && p.head_wt == nullptr && p.res_mode == 0 && p.relu <= 1 && p.f_cout % 32 == 0 &&
-                                      p.f_cout > 0 && p.f_cout <= 1024 && p.f_out != nullptr && p.f_chinv != nullptr && p.f_bias != nullptr && p.f_out_ldc % 4 == 0 &&
-                                      (p.f_res == nullptr || p.f_res_ldc % 4 == 0) && (double)M * p.f_out_ldc * 4.0 < 2147483648.0 &&
-                                      (p.f_res == nullptr || (double)M * p.f_res_ldc * 4.0 < 2147483648.0)),
-                "conv h2k: unsupported fused 1x1 tail");
-    }
-  } else if (p.wt_split_kind == 3) {
-    const int bn = p.wt_split_bn != 0 ? p.wt_split_bn : conv_split_bn(p.Cout);
-    ODT_CHECK((bm == 256 || (bm == 128 && bn >= 128)) && p.Cin % 16 == 0 && p.kh * p.kw <= 32, "conv split3: unsupported tile / shape");
-    ODT_CHECK(sk == 1 || (p.partial != nullptr && p.in2 == nullptr && (p.kh * p.kw * p.Cin >> 4) >= sk),
-              "conv split3: split-K needs a partial buffer, a single source and at least one stage per range");
-    ODT_CHECK(!p.wt_split_kwr || (bm == 256 && sk == 1 && p.kw == 3 && p.stride == 1 && p.in_Wa == p.Wo && p.in2 == nullptr),
-              "conv split3k: unsupported shape");
-  }
-  return 0;
-}
-
-int conv_finish(ConvParams& p, const Knobs& k) {
-  conv_prepare(p);
-  if (k.get(K_CONV_DEBUG).i != 0) p.debug = (int)k.get(K_CONV_DEBUG).i;
-  if (p.wt_split != nullptr) {
-    // the dense 1x1 reductions on two-wave fp16x2 tiles: double stages (conv_h2d.hip; ODT_CONV_H2_BK64=0: the single-stage kernel, A/B)
-    p.h2_bk64 = conv_h2d_fits(p) && !k.off(K_CONV_H2_BK64) ? 1 : 0;
-    // split-K combine pass: at most two blocks per CU (same-box A/B at b = 1: 2048 blocks 150.4, 512 167.5, 256 166.8, 128 159.6
-    // FPS): every block ends with a conditional atomicMax on the ONE range slot of the output, and the blocks of a short pass all
-    // find the slot empty -- 2040 same-address atomics serialised in L2 made this pass 35 us per call at b = 1 (1.2 ms of the
-    // 6.8 ms frame, profiles/r04_kernel_stats_bench_b1_single_before.txt)
-    const long capv = k.get_long(K_SPLIT_REDUCE_BLOCKS, 512L);
-    p.reduce_blocks = capv > 0 ? (int)capv : 512;
-    return conv_check(p);
-  }
-  // the exact-f32 kernel's tile / stages / loop style
-  const long M = (long)p.B * p.Ho * p.Wo;
-  const long tiles128 = ((M + 127) / 128) * ((p.Cout + 127) / 128);
-  int tile = (int)k.get_long(K_CONV_TILE, 0);   // 0 auto | 1: 128x64 | 2: 64x64 | 3: 128x128  (ODT_CONV_TILE: tuning / test knob)
-  // short reductions (K <= 384: EfficientNet / BiFPN 1x1 convs, the res2 / res3 1x1 layers): the
-  // 64x64 tile wins -- more workgroups per CU hide the per-tile prologue / epilogue that a two-to-
-  // twelve-slice main loop cannot amortise (measured per layer; ODT_CONV_SMALLK=0 for the A/B)
-  const bool smallk = !k.off(K_CONV_SMALLK);
-  const int Kfull = p.kh * p.kw * p.Cin + (p.in2 != nullptr ? p.Cin2 : 0);
-  if (tile == 0) tile = p.Cout <= 64 ? 1 : ((tiles128 < 384 || (smallk && Kfull <= 384)) ? 2 : 3);
-  // LDS stages: the single-stage / 3-workgroups-per-CU variant wins everywhere (measured per
-  // layer, profiles/) except the long 1x1 reductions on the 128x128 tile (res4 conv1, K = 1024:
-  // every slice is fresh HBM data, the two-slice register+LDS prefetch of ST = 2 hides it better).
-  int stages = (tile == 3 && p.kh * p.kw == 1 && p.Cin >= 1024) ? 2 : 1;
-  if (k.get(K_CONV_STAGES).i == 1 || k.get(K_CONV_STAGES).i == 2) stages = (int)k.get(K_CONV_STAGES).i;     // tuning knob: force 1 or 2
-  // Loop style (measured per layer, profiles/r01_conv_fine_vs_coarse*.txt): the fine-grained
-  // interleave keeps the matrix pipe of a CU busy when few workgroups share it (single-round
-  // launches: everything at b=1) and on long reductions; on short reductions with several rounds
-  // the workgroups in prologue / epilogue need the issue slots that a never-stalling main loop
-  // takes, and the coarse loop wins.
-  const int BMt = tile == 2 ? 64 : 128, BNt = tile == 3 ? 128 : 64;
-  const long tiles = ((M + BMt - 1) / BMt) * ((p.Cout + BNt - 1) / BNt);
-  const long slots = 256L * (stages == 2 ? 2 : (tile == 3 ? 3 : 4));
-  bool fine = stages == 2 || (tile != 2 && (tiles <= slots || tile == 1 || (Kfull >= 1024 && tiles >= 2 * slots)));
-  if (tile == 2) fine = tiles >= 384 && tiles <= slots;
-  if (k.get(K_CONV_FINE).c0 == '0' || k.get(K_CONV_FINE).c0 == '1') fine = k.get(K_CONV_FINE).c0 == '1';       // tuning knob: force 0 or 1
-  p.f32_tile = tile; p.f32_stages = stages; p.f32_fine = fine ? 1 : 0;
-  return conv_check(p);
-}
-
-int launch_conv(const ConvParams& p, const ConvParams* dev, hipStream_t stream) {
-  if (p.wt_split != nullptr) return launch_conv_split(p, dev, stream);
-  const int tile = p.f32_tile;
-  const bool fine = p.f32_fine != 0;
-  if (p.f32_stages == 1) {
-    if (tile == 1) { if (fine) launch_variant<4, 1, 1, 2, 1, true>(p, dev, stream); else launch_variant<4, 1, 1, 2, 1, false>(p, dev, stream); }
-    else if (tile == 2) { if (fine) launch_variant<2, 2, 1, 1, 1, true>(p, dev, stream); else launch_variant<2, 2, 1, 1, 1, false>(p, dev, stream); }
-    else { if (fine) launch_variant<2, 2, 2, 2, 1, true>(p, dev, stream); else launch_variant<2, 2, 2, 2, 1, false>(p, dev, stream); }
-  } else if (tile == 1) {                                        // 128 x 64
-    if (fine) launch_variant<4, 1, 1, 2, 2, true>(p, dev, stream); else launch_variant<4, 1, 1, 2, 2, false>(p, dev, stream);
-  } else if (tile == 2) {                                        // 64 x 64: fill the 256 CUs on small M
-    if (fine) launch_variant<2, 2, 1, 1, 2, true>(p, dev, stream); else launch_variant<2, 2, 1, 1, 2, false>(p, dev, stream);
-  } else {                                                       // 128 x 128
-    if (fine) launch_variant<2, 2, 2, 2, 2, true>(p, dev, stream); else launch_variant<2, 2, 2, 2, 2, false>(p, dev, stream);
-  }
-  ODT_HIP(hipGetLastError());
-  return 0;
+  return conv_check_variant(p);      // its row of the kernel table (conv_split.hip)
 }
 
 }  // namespace odt

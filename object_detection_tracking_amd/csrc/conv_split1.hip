@@ -341,20 +341,10 @@ __global__ void __launch_bounds__(256, 2) conv_split_kernel(const ConvParams* __
 
 }  // namespace
 
-int launch_conv_split1(const ConvParams& p, const ConvParams* dev, hipStream_t stream) {
-  const long M = (long)p.B * p.Ho * p.Wo;
-  const int bn = p.wt_split_bn != 0 ? p.wt_split_bn : conv_split_bn(p.Cout);
-  const int bm = conv_split_bm(p.Cout);
-  const unsigned grid = (unsigned)(((M + bm - 1) / bm) * (cout_padded(p.Cout) / bn));
-  if (p.trace != nullptr) {        // tuning: the stamped instantiations
-    if (bn == 256) hipLaunchKernelGGL((conv_split_kernel<2, 2, 4, true>), dim3(grid), dim3(256), 0, stream, dev);
-    else if (bn == 128) hipLaunchKernelGGL((conv_split_kernel<4, 1, 4, true>), dim3(grid), dim3(256), 0, stream, dev);
-    else hipLaunchKernelGGL((conv_split_kernel<4, 1, 2, true>), dim3(grid), dim3(256), 0, stream, dev);
-  } else if (bn == 256) hipLaunchKernelGGL((conv_split_kernel<2, 2, 4>), dim3(grid), dim3(256), 0, stream, dev);
-  else if (bn == 128) hipLaunchKernelGGL((conv_split_kernel<4, 1, 4>), dim3(grid), dim3(256), 0, stream, dev);
-  else hipLaunchKernelGGL((conv_split_kernel<4, 1, 2>), dim3(grid), dim3(256), 0, stream, dev);
-  ODT_HIP(hipGetLastError());
-  return 0;
+void conv_rows_split1(ConvKernelRow* t) {      // <WM, WN, TN>: 4 waves, tile WM * 64 x WN * TN * 32
+  ODT_CONV_ROW_T(t, SPLIT1_128x256, CF_SPLIT1, 128, 256, 256, 0, (conv_split_kernel<2, 2, 4>), (conv_split_kernel<2, 2, 4, true>));
+  ODT_CONV_ROW_T(t, SPLIT1_256x128, CF_SPLIT1, 256, 128, 256, 0, (conv_split_kernel<4, 1, 4>), (conv_split_kernel<4, 1, 4, true>));
+  ODT_CONV_ROW_T(t, SPLIT1_256x64, CF_SPLIT1, 256, 64, 256, 0, (conv_split_kernel<4, 1, 2>), (conv_split_kernel<4, 1, 2, true>));
 }
 
 }  // namespace odt

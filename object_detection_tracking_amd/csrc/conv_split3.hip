@@ -148,7 +148,7 @@ __global__ void __launch_bounds__(512, 2) conv_split3_kernel(const ConvParams* _
     }
   }
   // load stream position: (16-channel slice, tap) with the tap innermost; then the second source's slices
-  // (a split-K range starts inside the first source: launch_conv_split keeps split-K off for second-source convs)
+  // (a split-K range starts inside the first source: conv_select keeps split-K off for second-source convs)
   int l_cs = s_begin / ntaps, l_tap = s_begin - l_cs * ntaps;
   int l_kh = l_tap / p.kw, l_kw = l_tap - l_kh * p.kw;
   bool l_src2 = false;
@@ -639,46 +639,21 @@ __global__ void __launch_bounds__(256) split_reduce_kernel(const ConvParams* __r
 
 }  // namespace
 
-template <int WM, int WN, int TN>
-static void launch_split3(const ConvParams& p, const ConvParams* dev, unsigned grid, hipStream_t stream) {
-  if (p.trace != nullptr) hipLaunchKernelGGL((conv_split3_kernel<WM, WN, TN, true>), dim3(grid), dim3(512), 0, stream, dev);
-  else hipLaunchKernelGGL((conv_split3_kernel<WM, WN, TN, false>), dim3(grid), dim3(512), 0, stream, dev);
-}
-
-
 void launch_split_reduce(const ConvParams& p, const ConvParams* dev, hipStream_t stream) {
   const long chunks = (long)p.B * p.Ho * p.Wo * (cout_padded(p.Cout) / 4);
-  const long blocks = (chunks + 255) / 256, cap = p.reduce_blocks;     // (grid-stride; conv_finish sets the cap)
+  const long blocks = (chunks + 255) / 256, cap = p.reduce_blocks;     // (grid-stride; conv_select sets the cap)
   hipLaunchKernelGGL(split_reduce_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, stream, dev);
 }
 
-int launch_conv_split3(const ConvParams& p, const ConvParams* dev, hipStream_t stream) {
-  const long M = (long)p.B * p.Ho * p.Wo;
-  const int bn = p.wt_split_bn != 0 ? p.wt_split_bn : conv_split_bn(p.Cout);
-  const int bm = p.wt_split_bm;
-  const int sk = p.splitk > 1 ? p.splitk : 1;
-  const unsigned grid = (unsigned)(((M + bm - 1) / bm) * (cout_padded(p.Cout) / bn) * sk);
-  if (p.wt_split_kwr) {
-    if (bn == 256) {
-      if (p.trace != nullptr) hipLaunchKernelGGL((conv_split3k_kernel<4, true>), dim3(grid), dim3(512), 0, stream, dev);
-      else hipLaunchKernelGGL((conv_split3k_kernel<4, false>), dim3(grid), dim3(512), 0, stream, dev);
-    } else if (bn == 128) {
-      if (p.trace != nullptr) hipLaunchKernelGGL((conv_split3k_kernel<2, true>), dim3(grid), dim3(512), 0, stream, dev);
-      else hipLaunchKernelGGL((conv_split3k_kernel<2, false>), dim3(grid), dim3(512), 0, stream, dev);
-    } else {
-      hipLaunchKernelGGL((conv_split3k_kernel<1, false>), dim3(grid), dim3(512), 0, stream, dev);
-    }
-  } else if (bm == 256) {
-    if (bn == 256) launch_split3<4, 2, 4>(p, dev, grid, stream);
-    else if (bn == 128) launch_split3<4, 2, 2>(p, dev, grid, stream);
-    else launch_split3<4, 2, 1>(p, dev, grid, stream);
-  } else {
-    if (bn == 256) launch_split3<2, 4, 2>(p, dev, grid, stream);
-    else launch_split3<2, 4, 1>(p, dev, grid, stream);
-  }
-  if (sk > 1) launch_split_reduce(p, dev, stream);
-  ODT_HIP(hipGetLastError());
-  return 0;
+void conv_rows_split3(ConvKernelRow* t) {
+  ODT_CONV_ROW_T(t, SPLIT3K_256x256, CF_SPLIT3, 256, 256, 512, CVF_KWR, (conv_split3k_kernel<4, false>), (conv_split3k_kernel<4, true>));
+  ODT_CONV_ROW_T(t, SPLIT3K_256x128, CF_SPLIT3, 256, 128, 512, CVF_KWR, (conv_split3k_kernel<2, false>), (conv_split3k_kernel<2, true>));
+  ODT_CONV_ROW(t, SPLIT3K_256x64, CF_SPLIT3, 256, 64, 512, CVF_KWR, (conv_split3k_kernel<1, false>));
+  ODT_CONV_ROW_T(t, SPLIT3_256x256, CF_SPLIT3, 256, 256, 512, 0, (conv_split3_kernel<4, 2, 4, false>), (conv_split3_kernel<4, 2, 4, true>));
+  ODT_CONV_ROW_T(t, SPLIT3_256x128, CF_SPLIT3, 256, 128, 512, 0, (conv_split3_kernel<4, 2, 2, false>), (conv_split3_kernel<4, 2, 2, true>));
+  ODT_CONV_ROW_T(t, SPLIT3_256x64, CF_SPLIT3, 256, 64, 512, 0, (conv_split3_kernel<4, 2, 1, false>), (conv_split3_kernel<4, 2, 1, true>));
+  ODT_CONV_ROW_T(t, SPLIT3_128x256, CF_SPLIT3, 128, 256, 512, 0, (conv_split3_kernel<2, 4, 2, false>), (conv_split3_kernel<2, 4, 2, true>));
+  ODT_CONV_ROW_T(t, SPLIT3_128x128, CF_SPLIT3, 128, 128, 512, 0, (conv_split3_kernel<2, 4, 1, false>), (conv_split3_kernel<2, 4, 1, true>));
 }
 
 }  // namespace odt

@@ -287,14 +287,15 @@ __global__ void __launch_bounds__(512, 2) conv_stem_kernel(const ConvParams* __r
 // conv0 posed as the plan's 7 x 1 conv over 8-pixel x 4-channel rows, fp16x2 weight image with a 64-wide n-tile, ReLU,
 // `out` = the POOLED map [B, out_H, out_W, out_ldc]
 bool conv_stem_fits(const ConvParams& p) {
-  return p.wt_split != nullptr && p.wt_split_kind == 2 && p.wt_split_bn == 64 && p.Cout == 64 && p.kh == 7 && p.kw == 1 && p.Cin == 32 &&
+  const ConvKernelRow& r = conv_variant_row(p.variant);
+  return p.wt_split != nullptr && r.family == CF_H2 && r.bn == 64 && p.Cout == 64 && p.kh == 7 && p.kw == 1 && p.Cin == 32 &&
          p.in_ldc == 4 && p.stride == 2 && p.dil == 1 && p.pad_t == 0 && p.pad_l == 0 && p.relu == 1 && p.res_mode == 0 &&
          p.in2 == nullptr && p.splitk <= 1 && p.head_wt == nullptr && p.f_wt == nullptr && p.nlvl <= 1 && p.in_amax != nullptr &&
          p.h2_chinv != nullptr && p.H == p.in_Ha && p.W == p.in_Wa && p.in_Wa >= 2 * p.Wo + 6 && p.in_Ha >= 2 * p.Ho + 5 &&
          p.out_ldc >= 64 && p.out_ldc % 4 == 0;
 }
 
-int launch_conv_stem(const ConvParams& p, const ConvParams* dev, hipStream_t stream) {
+int conv_stem_grid(const ConvParams& p, unsigned* grid) {
   // one persistent workgroup per CU of the CURRENT device (handles on different devices / partitions differ; several
   // host threads may launch at once): a per-device table, each slot written once with a value that depends on the device
   // only (a benign double fill writes the same number)
@@ -311,10 +312,12 @@ int launch_conv_stem(const ConvParams& p, const ConvParams* dev, hipStream_t str
   const long ntiles = (long)p.B * ((p.out_H + StemCfg::PY - 1) / StemCfg::PY) * ((p.out_W + StemCfg::PX - 1) / StemCfg::PX);
   const int cap = (p.debug >> 20) & 0x3ff;   // (test knob ODT_STEM_GRID through fuse_stem: fewer workgroups, several tiles each on small frames)
   const long want = cap > 0 && cap < ncu ? cap : ncu;
-  const unsigned grid = (unsigned)(ntiles < want ? ntiles : want);
-  hipLaunchKernelGGL(conv_stem_kernel, dim3(grid), dim3(512), 0, stream, dev);
-  ODT_HIP(hipGetLastError());
+  *grid = (unsigned)(ntiles < want ? ntiles : want);
   return 0;
+}
+
+void conv_rows_stem(ConvKernelRow* t) {      // (bm x bn: the weight image's tile; the grid is conv_stem_grid's)
+  ODT_CONV_ROW(t, H2_STEM, CF_H2, 128, 64, 512, CVF_STEM, (conv_stem_kernel));
 }
 
 }  // namespace odt

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <vector>
 
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
@@ -83,15 +84,15 @@ struct ConvParams {
   // optional bf16-piece image of `wt` (conv_make_split_weights): the layer runs on the bf16x3
   // split kernel (conv_split.hip: f32 result through six exact bf16 MFMA products per MAC)
   const void* wt_split;
-  int wt_split_kind;   // which kernel family the image was laid out for: 1 one-stage BK = 32 (conv_split_kernel, the 64-wide
-                       // layers) | 3 conv_split3_kernel / conv_split3k_kernel (8 waves, LDS-DMA weight stages) | 2 conv_h2_kernel /
-                       // conv_h2k_kernel (fp16x2 pieces)
-  int wt_split_bm;     // kind 3: rows of the block tile (256, or 128 when 256-row tiles would not fill the chip)
-  int wt_split_bn;     // n-tile width the image was laid out for (kind 3 may use 128 on wider layers; 0: conv_split_bn(Cout))
-  // split-K (conv_split3_kernel only): the reduction is cut into `splitk` contiguous ranges of stages, one workgroup per
+  // which kernel instantiation runs this record: a row of the conv kernel table (ConvVariant below; conv_use_variant is the
+  // only writer).  HOST-ONLY, like the slots beside it -- of the launch choices the kernels read `splitk` alone.  The row
+  // names the family the weight image was laid out for, the block tile bm x bn and the kw-reuse / double-stage / fused
+  // forms; 0: none chosen (yet).
+  int variant;
+  int host_unused0_[3];
+  // split-K (the conv_split3 and fp16x2 kernels): the reduction is cut into `splitk` contiguous ranges of stages, one workgroup per
   // (tile, range); each writes its raw f32 partial tile to partial[range][M][Cout] and split_reduce_kernel adds them in
   // range order (deterministic) and applies bias / residual / activation.  For layers whose tiles cannot fill the chip.
-  int wt_split_kwr;    // kind 3: 1 = conv_split3k_kernel (the three kw taps of a (slice, kh) group share one staged run of pixels)
   int splitk;          // 0 / 1: off
   float* partial;      // scratch [splitk][M][Cout] (plan-owned, shared by the plan's split-K layers)
   // optional fused 1x1 head behind this conv (conv_split3 kernels whose n-tile is the whole Cout = 256: the RPN 3x3 conv +
@@ -107,14 +108,14 @@ struct ConvParams {
   int lvl_start[5];
   int lvl_stride;
   const float* lvl_scale;
-  // fp16x2 pieces (wt_split_kind == 2, conv_h2.hip): the A operand is scaled by a power of two taken from the recorded |max|
+  // fp16x2 pieces (CF_H2 rows, conv_h2.hip): the A operand is scaled by a power of two taken from the recorded |max|
   // of the source tensor(s) -- a u32 holding the f32 bit pattern, written by the producers' epilogues (out_amax: atomic max
   // over the stored values; the plan clears the slots at the start of a forward) -- and the weight image's column n by
   // 2^t_n; the epilogue multiplies the accumulators by h2_chinv[n] = 2^-t_n and by the inverse of the A scale.
-  const unsigned* in_amax;   // |max| of `in` (required for kind 2)
+  const unsigned* in_amax;   // |max| of `in` (required for the CF_H2 rows)
   const unsigned* in2_amax;  // ... of `in2`
   unsigned* out_amax;        // where this conv records the |max| of what it stores (any split kernel), or nullptr
-  const float* h2_chinv;     // [cout_padded(Cout)] (kind 2)
+  const float* h2_chinv;     // [cout_padded(Cout)] (CF_H2 rows)
   const float* head_wt;    // [Cout][16] (k-major, column 15 zero) or nullptr
   const float* head_bias;  // [16]
   float* head_out;         // [M][head_ldc] dense rows (m = (n, ho, wo))
@@ -132,23 +133,79 @@ struct ConvParams {
   float* f_out;            // [M][f_out_ldc]
   unsigned* f_out_amax;    // range slot of f_out or nullptr
   int f_cout, f_out_ldc, f_res_ldc, f_relu;
-  // conv0 + pool0 in one kernel (conv_stem.hip; fuse_stem): `out` is the 3x3 / stride-2 max-pooled map [B, out_H, out_W, out_ldc]
-  // of the conv's [B, Ho, Wo, Cout] result, which is not written
-  int stem_pool;
-  // launch choices (conv_finish; the launchers read these, never a knob)
-  int f32_tile, f32_stages, f32_fine;   // exact-f32 kernel: 1 128x64 | 2 64x64 | 3 128x128 tile; LDS stages; fine-grained loop
-  int h2_bk64;         // two-wave dense 1x1 fp16x2 tiles on conv_h2d_kernel (conv_h2d_fits; ODT_CONV_H2_BK64=0: off)
-  int reduce_blocks;   // block cap of the split-K combine pass (ODT_SPLIT_REDUCE_BLOCKS)
+  int host_unused1_[5];
+  int reduce_blocks;   // block cap of the split-K combine pass (ODT_SPLIT_REDUCE_BLOCKS; conv_select)
 };
+// the device record does not move when a host-only slot changes its meaning (tests/test_kernel_resources.py: one awkward
+// field once pushed the kernels' copy of it into scratch)
+static_assert(sizeof(ConvParams) == 432 && offsetof(ConvParams, variant) == 208 && offsetof(ConvParams, splitk) == 224 &&
+              offsetof(ConvParams, nlvl) == 240 && offsetof(ConvParams, reduce_blocks) == 428, "ConvParams layout");
 // fills the derived fields (multiply-shift divisors)
 void conv_prepare(ConvParams& p);
-// finishes a record: conv_prepare, the ODT_CONV_DEBUG bits and every launch choice above, then conv_check; once per record,
-// before it is copied to the device (the plan's upload_conv_records, the stand-alone conv calls)
-int conv_finish(ConvParams& p, const Knobs& k);
-int conv_check(const ConvParams& p);      // the launch preconditions of a record (shape, 32-bit offsets, split kernel family)
-// dispatch of a finished, checked record; dev: its device copy (the kernels read their parameters from there)
-int launch_conv(const ConvParams& p, const ConvParams* dev, hipStream_t stream);
 double conv_flops(const ConvParams& p);   // algorithmic 2*M*N*K
+
+// ---- the conv kernel table (conv_split.hip owns the lookup; each family file contributes its rows and launch thunks) ----
+// One row per kernel instantiation a conv record can run on.  Selection (conv_select), validation (conv_check) and the
+// one launcher (launch_conv) all read this table; nothing else knows which (tile, form) combinations exist.
+enum ConvFamily : int { CF_F32 = 0, CF_SPLIT1 = 1, CF_H2 = 2, CF_SPLIT3 = 3 };   // exact f32 | one-stage bf16x3 | fp16x2 | 8-wave bf16x3
+// (the split families' values are also the layout ids of their weight images: conv_make_split_weights)
+enum ConvVariantFlag : unsigned {
+  CVF_KWR = 1u,      // kw-reuse kernel: the three kw taps of a (slice, kh) group share one staged run of pixels
+  CVF_DSTAGE = 2u,   // conv_h2d_kernel: double stages for the dense 1x1 reductions on two-wave tiles
+  CVF_FTAIL = 4u,    // conv_h2k_kernel<.., FUSE>: the bottleneck's conv3 evaluated from conv2's accumulators (ConvParams::f_wt)
+  CVF_STEM = 8u,     // conv_stem_kernel: conv0 + pool0, persistent workgroups; `out` is the 3x3 / stride-2 max-pooled map
+                     // [B, out_H, out_W, out_ldc] of the conv's [B, Ho, Wo, Cout] result, which is not written
+  CVF_ST2 = 16u,     // exact f32: two LDS stages
+  CVF_FINE = 32u,    // exact f32: fine-grained loop
+};
+#define ODT_CONV_VARIANT_LIST(X)                                                                                                   \
+  X(F32_128x64_S1) X(F32_128x64_S1_FINE) X(F32_128x64_S2) X(F32_128x64_S2_FINE) X(F32_64x64_S1) X(F32_64x64_S1_FINE)              \
+  X(F32_64x64_S2) X(F32_64x64_S2_FINE) X(F32_128x128_S1) X(F32_128x128_S1_FINE) X(F32_128x128_S2) X(F32_128x128_S2_FINE)          \
+  X(SPLIT1_128x256) X(SPLIT1_256x128) X(SPLIT1_256x64)                                                                            \
+  X(SPLIT3_256x256) X(SPLIT3_256x128) X(SPLIT3_256x64) X(SPLIT3_128x256) X(SPLIT3_128x128)                                        \
+  X(SPLIT3K_256x256) X(SPLIT3K_256x128) X(SPLIT3K_256x64)                                                                         \
+  X(H2_64x64) X(H2_64x128) X(H2_512x64) X(H2_128x64) X(H2_256x256) X(H2_256x128) X(H2_128x128) X(H2D_64x64) X(H2D_64x128)         \
+  X(H2K_256x256) X(H2K_256x128) X(H2K_512x64) X(H2K_256x64) X(H2KF_256x64) X(H2KF_256x128) X(H2KF_256x256) X(H2_STEM)
+enum ConvVariant : int {
+  CV_NONE = 0,
+#define ODT_CONV_VARIANT_ENUM(n) CV_##n,
+  ODT_CONV_VARIANT_LIST(ODT_CONV_VARIANT_ENUM)
+#undef ODT_CONV_VARIANT_ENUM
+  CV_COUNT
+};
+typedef void (*ConvLaunchFn)(const ConvParams* dev, unsigned grid, hipStream_t stream);
+struct ConvKernelRow {
+  const char* name;              // stable: tests/golden/conv_choice.json and the tools name rows by it
+  int family;                    // ConvFamily
+  int bm, bn, threads;           // block tile, threads per workgroup
+  unsigned flags;                // ConvVariantFlag
+  ConvLaunchFn launch;
+  ConvLaunchFn launch_traced;    // the TRACE = true twin, or nullptr: a trace request keeps running `launch`
+};
+// a family file's row of the conv kernel table (odt_common.hpp: ConvKernelRow) with its launch thunk(s); kernels are passed in
+// parentheses, as to hipLaunchKernelGGL
+#define ODT_CONV_THUNK(threads, kern) \
+  [](const ConvParams* dev, unsigned grid, hipStream_t st) { hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, st, dev); }
+#define ODT_CONV_ROW(t, id, fam, bm, bn, threads, flags, kern) \
+  t[CV_##id] = ConvKernelRow{#id, fam, bm, bn, threads, flags, ODT_CONV_THUNK(threads, kern), nullptr}
+#define ODT_CONV_ROW_T(t, id, fam, bm, bn, threads, flags, kern, kern_traced) \
+  t[CV_##id] = ConvKernelRow{#id, fam, bm, bn, threads, flags, ODT_CONV_THUNK(threads, kern), ODT_CONV_THUNK(threads, kern_traced)}
+const ConvKernelRow& conv_variant_row(int variant);      // (CV_NONE / out of range: an empty row, launch == nullptr)
+// the row of a (family, tile, form), CV_NONE if the table has none
+int conv_variant_find(int family, int bm, int bn, unsigned flags);
+// the fused-tail row that runs a kw-reuse fp16x2 record's weight image (512 x 64 tiles: the 256-row form), CV_NONE if none
+int conv_variant_fused_tail(int variant);
+// sets a record's variant by hand (the fusions, the stand-alone op entry points); validated like any other by conv_check
+void conv_use_variant(ConvParams& p, int variant, int splitk = 1, int reduce_blocks = 0);
+// each family file's rows (conv_igemm.hip, conv_split1.hip, conv_split3.hip, conv_h2.hip, conv_h2d.hip, conv_h2k.hip, conv_stem.hip)
+void conv_rows_f32(ConvKernelRow* t);
+void conv_rows_split1(ConvKernelRow* t);
+void conv_rows_split3(ConvKernelRow* t);
+void conv_rows_h2(ConvKernelRow* t);
+void conv_rows_h2d(ConvKernelRow* t);
+void conv_rows_h2k(ConvKernelRow* t);
+void conv_rows_stem(ConvKernelRow* t);
+
 // bf16x3 split path (conv_split.hip).  ConvPolicy: which convs take it and which kernel family -- per handle, fixed at
 // plan build from odt_config and the handle's ODT_CONV_* overrides (conv_policy_with_knobs); a stand-alone conv call
 // resolves it under the call's knobs.
@@ -177,21 +234,38 @@ struct ConvPolicy {
 ConvPolicy conv_policy_default();
 ConvPolicy conv_policy_with_knobs(ConvPolicy q, const Knobs& k);
 bool conv_split_supported(const ConvParams& p);
-// the layer is supported AND large enough to fill the chip with the split tiles
-bool conv_split_wanted(const ConvParams& p, const ConvPolicy& q);
+// THE selection: which row runs this conv under this policy and these knobs.  Pure: reads the shape fields of p and whether
+// its sources come with a recorded range (in_amax / in2_amax), nothing else.  A CF_F32 row = the exact-f32 kernel; a split
+// row names the weight-image layout (family, bn) that conv_make_split_weights must build before the launch.
+struct ConvChoice {
+  int variant, splitk, reduce_blocks;
+};
+ConvChoice conv_select(const ConvParams& p, const ConvPolicy& q, const Knobs& k);
+// finishes a record: conv_prepare, the ODT_CONV_DEBUG bits, the exact-f32 row where no split image is attached (it
+// depends on the rows of THIS record -- a plan cuts large convs into batch ranges), then conv_check; once per record, before
+// it is copied to the device (the plan's upload_conv_records, the stand-alone conv calls)
+int conv_finish(ConvParams& p, const Knobs& k);
+int conv_check(const ConvParams& p);      // the launch preconditions of a record: shape, 32-bit offsets (conv_igemm.hip), then ...
+int conv_check_variant(const ConvParams& p);      // ... its row of the table against the shape (conv_split.hip)
+// THE launcher of a finished, checked record: grid and split-K combine pass from its row; dev: its device copy (the kernels
+// read their parameters from there)
+int launch_conv(const ConvParams& p, const ConvParams* dev, hipStream_t stream);
+// shape predicates shared by selection and validation (each exists once)
+bool conv_kwr_fits(const ConvParams& p);           // the kw-reuse kernels: stride-1 KH x 3 convs over rows of the output's pitch
+bool conv_h2_sources_ok(const ConvParams& p);      // fp16x2 allowed for this layer: recorded range(s), 32-channel slices
+bool conv_h2d_fits(const ConvParams& p);           // conv_h2d.hip: dense same-size 1x1 with at least two double stages
+bool conv_stem_fits(const ConvParams& p);          // conv_stem.hip: the plan's conv0 on 64-wide fp16x2 tiles
+int conv_stem_grid(const ConvParams& p, unsigned* grid);   // one persistent workgroup per CU of the current device
 size_t conv_split_weight_bytes(int Cout, int K);
 int conv_split_bn(int Cout);   // n-tile width of the split configuration for this Cout (0: none)
 int conv_split_bm(int Cout);
-// picks the split kernel family / tile for a conv that conv_split_wanted() accepted (fills wt_split_kind / wt_split_bm)
-void conv_split_choose(ConvParams& p, const ConvPolicy& q);
-// builds the bf16-piece image of p.wt for p.wt_split_kind (conv_split_choose first)
+// builds the weight image of p.wt in the layout of p's row (conv_use_variant first)
 // wt_src: source weights if not p.wt; kscale[K]: per-k factor folded into the weights first (single-source 1x1 convs: a
 // per-input-channel gate, e.g. squeeze-excite, applied to the weights instead of the activations)
 int conv_make_split_weights(const ConvParams& p, void* img_dev, hipStream_t stream, const float* wt_src = nullptr,
                             const float* kscale = nullptr);
 int conv_scale_weights(const float* wt, const float* kscale, int Cout, int K, float* out, hipStream_t stream);
-int launch_conv_split(const ConvParams& p, const ConvParams* dev, hipStream_t stream);
-// fp16x2 pieces (conv_h2.hip; wt_split_kind == 2): the image (conv_make_split_weights builds it) carries the per-column
+// fp16x2 pieces (conv_h2.hip; CF_H2 rows): the image (conv_make_split_weights builds it) carries the per-column
 // inverse scales behind the pieces -- ConvParams::h2_chinv must point there; launch_tensor_amax records the |max| of a dense
 // array for a source tensor no producer recorded one for (stand-alone calls)
 const float* conv_h2_chinv(const void* img, int Cout, int K);
@@ -203,9 +277,6 @@ int launch_tensor_amax(const float* x, size_t n, unsigned* slot, hipStream_t str
 size_t conv_h2f_weight_bytes(int Cout, int K);
 const float* conv_h2f_chinv(const void* img, int Cout, int K);
 int conv_make_h2f_weights(const float* wt, int Cout, int K, void* img_dev, hipStream_t stream);
-bool conv_stem_fits(const ConvParams& p);          // conv_stem.hip: the plan's conv0 on the fp16x2 family
-bool conv_h2d_fits(const ConvParams& p);           // conv_h2d.hip: double-stage two-wave tiles for the dense 1x1 fp16x2 layers
-int launch_conv_stem(const ConvParams& p, const ConvParams* dev, hipStream_t stream);
 bool conv_h2f_fusable(const ConvParams& a, const ConvParams& b);   // a: the KH x 3 producer, b: the 1x1 conv reading a.out
 size_t conv_split_partial_bytes(const ConvParams& p);   // scratch a split-K conv needs (0: none)
 
@@ -248,7 +319,7 @@ int launch_dwconv(const DwConvParams& p, hipStream_t stream);
 struct MbExpandDwParams {
   const float* x;        // block input [B,H,W,in_ldc]; K of the expand GEMM = in_ldc (pad channels: zero weights)
   int B, H, W, in_ldc;
-  const void* w_img;     // bf16x3 piece image of the expand weights [lmid][in_ldc] (conv_make_split_weights, kind 1, n-tile 64)
+  const void* w_img;     // bf16x3 piece image of the expand weights [lmid][in_ldc] (conv_make_split_weights, the SPLIT1_256x64 row's layout)
   const float* e_bias;   // [mid] folded BN shift of the expand conv
   int mid, lmid;         // expanded channels, their stride (multiple of 64)
   const float* dw_wt;    // [k*k][lmid]  (BN scale folded, pad channels zero)

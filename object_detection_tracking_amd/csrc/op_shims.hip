@@ -44,7 +44,8 @@ int run_conv(ConvParams q, const Knobs& kn) {
     }
   } tmp;
   const ConvPolicy pol = conv_policy_with_knobs(conv_policy_default(), kn);
-  if (conv_split_wanted(q, pol)) {
+  ConvChoice ch = conv_select(q, pol, kn);
+  if (conv_variant_row(ch.variant).family != CF_F32) {
     const int Ksp = q.kh * q.kw * q.Cin + (q.in2 != nullptr ? q.Cin2 : 0);
     ODT_HIP(hipMalloc(&tmp.img, conv_split_weight_bytes(q.Cout, Ksp)));
     if (pol.family == 2 && q.in_amax == nullptr) {      // fp16x2 pieces need the sources' |max|: nobody recorded it for a stand-alone call
@@ -58,10 +59,11 @@ int run_conv(ConvParams q, const Knobs& kn) {
         if (launch_tensor_amax(q.in2, (size_t)q.B * q.in2_Ha * q.in2_Wa * q.in2_ldc, tmp.amax + kAmaxWays, nullptr)) return 1;
         q.in2_amax = tmp.amax + kAmaxWays;
       }
+      ch = conv_select(q, pol, kn);       // (with the ranges: whether a layer takes the split kernels does not depend on them, which ones does)
     }
-    conv_split_choose(q, pol);
+    conv_use_variant(q, ch.variant, ch.splitk, ch.reduce_blocks);
     if (conv_make_split_weights(q, tmp.img, nullptr)) return 1;
-    if (q.wt_split_kind == 2) q.h2_chinv = conv_h2_chinv(tmp.img, q.Cout, Ksp);
+    if (conv_variant_row(q.variant).family == CF_H2) q.h2_chinv = conv_h2_chinv(tmp.img, q.Cout, Ksp);
     q.wt_split = tmp.img;
     if (conv_split_partial_bytes(q) > 0) ODT_HIP(hipMalloc((void**)&tmp.partial, conv_split_partial_bytes(q)));
     q.partial = tmp.partial;
@@ -330,7 +332,7 @@ int odt_op_bottleneck_tail(int device, const float* in, int B, int H, int W, int
   a.B = B; a.H = H; a.W = W; a.Cin = C; a.in_ldc = C; a.in_Ha = H; a.in_Wa = W; a.Ho = H; a.Wo = W; a.Cout = C;
   a.kh = 3; a.kw = 3; a.stride = 1; a.dil = dil; a.pad_t = dil; a.pad_l = dil;
   a.out_H = H; a.out_W = W; a.out_ldc = C; a.relu = 1;
-  a.wt_split_kind = 2; a.wt_split_bm = 256; a.wt_split_bn = C; a.wt_split_kwr = 1; a.splitk = 1;
+  conv_use_variant(a, conv_variant_find(CF_H2, 256, C, CVF_KWR));
   a.in_amax = amax.d; a.out_amax = amax.d + kAmaxWays; a.debug = 0x400;
   conv_prepare(a);
   if (img2.alloc((conv_split_weight_bytes(C, 9 * C) + 3) / 4) || conv_make_split_weights(a, img2.d, nullptr)) return 1;
@@ -341,8 +343,7 @@ int odt_op_bottleneck_tail(int device, const float* in, int B, int H, int W, int
   b.kh = 1; b.kw = 1; b.stride = 1; b.dil = 1;
   b.out_H = H; b.out_W = W; b.out_ldc = C3; b.relu = relu3 ? 1 : 0;
   b.res_mode = res ? 1 : 0; b.res_H = H; b.res_W = W; b.res_ldc = C3;
-  b.wt_split_kind = 2; b.wt_split_bm = 256; b.wt_split_bn = C3 % 256 == 0 ? 256 : (C3 % 128 == 0 ? 128 : 64); b.splitk = 1;
-  if (b.wt_split_bn == 64) b.wt_split_bm = 128;
+  conv_use_variant(b, C3 % 256 == 0 ? CV_H2_256x256 : (C3 % 128 == 0 ? CV_H2_256x128 : CV_H2_128x64));
   b.in_amax = amax.d + kAmaxWays; b.out_amax = amax.d + 2 * kAmaxWays; b.debug = 0x400;
   conv_prepare(b);
   if (img3.alloc((conv_split_weight_bytes(C3, C) + 3) / 4) || conv_make_split_weights(b, img3.d, nullptr)) return 1;
@@ -351,17 +352,18 @@ int odt_op_bottleneck_tail(int device, const float* in, int B, int H, int W, int
   if (rec.alloc(2)) return 1;
   if (fuse) {
     ODT_CHECK(conv_h2f_fusable(a, b), "odt_op_bottleneck_tail: this pair is not fusable");
+    conv_use_variant(a, conv_variant_fused_tail(a.variant));
     if (imgf.alloc((conv_h2f_weight_bytes(C3, C) + 3) / 4) || conv_make_h2f_weights(dw3.d, C3, C, imgf.d, nullptr)) return 1;
     a.f_wt = imgf.d; a.f_chinv = conv_h2f_chinv(imgf.d, C3, C); a.f_bias = db3.d; a.f_res = b.res; a.f_res_ldc = C3;
     a.f_out = dout.d; a.f_out_ldc = C3; a.f_cout = C3; a.f_relu = b.relu; a.f_out_amax = amax.d + 2 * kAmaxWays;
     a.out = nullptr; a.out_amax = nullptr;
     ConvParams recs[2] = {a, b};
     if (conv_check(a) || rec.put(recs)) return 1;
-    if (launch_conv_split(a, rec.d, nullptr)) return 1;
+    if (launch_conv(a, rec.d, nullptr)) return 1;
   } else {
     ConvParams recs[2] = {a, b};
     if (conv_check(a) || conv_check(b) || rec.put(recs)) return 1;
-    if (launch_conv_split(a, rec.d, nullptr) || launch_conv_split(b, rec.d + 1, nullptr)) return 1;
+    if (launch_conv(a, rec.d, nullptr) || launch_conv(b, rec.d + 1, nullptr)) return 1;
   }
   ODT_HIP(hipDeviceSynchronize());
   return dout.get(out, M * C3);
@@ -392,22 +394,70 @@ int odt_op_stem(int device, const float* frame_pad, int B, int Hp, int Wp, const
   p.in = di.d; p.wt = dw.d; p.bias = db.d; p.out = dmap.d;
   p.B = B; p.H = Hp; p.W = Wa; p.Cin = 32; p.in_ldc = 4; p.in_Ha = Hp; p.in_Wa = Wa; p.Ho = Ho0; p.Wo = Wo0; p.Cout = 64;
   p.kh = 7; p.kw = 1; p.stride = 2; p.dil = 1; p.out_H = Ho0; p.out_W = Wo0; p.out_ldc = 64; p.relu = 1;
-  p.wt_split_kind = 2; p.wt_split_bm = 128; p.wt_split_bn = 64; p.splitk = 1;
+  conv_use_variant(p, CV_H2_128x64);
   p.in_amax = amax.d; p.out_amax = amax.d + kAmaxWays;
   conv_prepare(p);
   if (img.alloc((conv_split_weight_bytes(64, 224) + 3) / 4) || conv_make_split_weights(p, img.d, nullptr)) return 1;
   p.wt_split = img.d; p.h2_chinv = conv_h2_chinv(img.d, 64, 224);
   if (fuse) {
     ODT_CHECK(conv_stem_fits(p), "odt_op_stem: shape not taken by the stem kernel");
-    p.out = dout.d; p.out_H = Hq; p.out_W = Wq; p.stem_pool = 1;
+    p.out = dout.d; p.out_H = Hq; p.out_W = Wq; conv_use_variant(p, CV_H2_STEM);
     if (grid > 0) p.debug |= (grid & 0x3ff) << 20;
-    if (conv_check(p) || rec.put(&p) || launch_conv_split(p, rec.d, nullptr)) return 1;
+    if (conv_check(p) || rec.put(&p) || launch_conv(p, rec.d, nullptr)) return 1;
   } else {
-    if (conv_check(p) || rec.put(&p) || launch_conv_split(p, rec.d, nullptr)) return 1;
+    if (conv_check(p) || rec.put(&p) || launch_conv(p, rec.d, nullptr)) return 1;
     if (launch_maxpool3x3s2(dmap.d, B, Ho0, Wo0, 64, dout.d, Hq, Wq, nullptr)) return 1;
   }
   ODT_HIP(hipDeviceSynchronize());
   return dout.get(out, nout);
+}
+
+// Which kernel would run this conv?  Host only: the record is built from the shape with placeholder (never dereferenced)
+// pointers and goes the way of a stand-alone conv call -- conv_check, the policy under the call's knobs, conv_select,
+// conv_finish -- up to, not including, the weight image and the launch.  No device is touched.
+int odt_op_conv_choice(const int* shape, int conv_arith, int conv_split_family, int* out, char* name, int name_cap) {
+  ODT_CHECK(shape && out, "odt_op_conv_choice: null argument");
+  static float ph_f[4]; static unsigned ph_u[4];
+  for (int i = 0; i < ODT_CONV_CHOICE_OUT; ++i) out[i] = 0;
+  if (name && name_cap > 0) name[0] = 0;
+  const int* s = shape;
+  ConvParams q; std::memset(&q, 0, sizeof(q));
+  q.in = ph_f; q.wt = ph_f; q.bias = ph_f; q.out = ph_f;
+  q.B = s[0]; q.H = s[1]; q.W = s[2]; q.Cin = s[3]; q.Cout = s[4]; q.kh = s[5]; q.kw = s[6]; q.stride = s[7]; q.dil = s[8];
+  q.pad_t = s[9]; q.pad_l = s[9]; q.Ho = s[10]; q.Wo = s[11]; q.in_Wa = s[12]; q.in_Ha = q.H;
+  q.in_ldc = s[16] > 0 ? s[16] : q.Cin; q.out_ldc = s[17] > 0 ? s[17] : q.Cout;
+  q.out_H = q.Ho; q.out_W = q.Wo;
+  if (s[13] > 0) { q.in2 = ph_f; q.Cin2 = s[13]; q.in2_ldc = s[13]; q.in2_Ha = q.Ho; q.in2_Wa = q.Wo; q.in2_stride = 1; }
+  q.res_mode = s[14];
+  if (q.res_mode != 0) {
+    q.res = ph_f; q.res_ldc = q.out_ldc;
+    q.res_H = q.res_mode == 2 ? (q.Ho + 1) / 2 : q.Ho; q.res_W = q.res_mode == 2 ? (q.Wo + 1) / 2 : q.Wo;
+  }
+  if (s[15]) { q.in_amax = ph_u; if (q.in2 != nullptr) q.in2_amax = ph_u; }
+  const Knobs kn = knobs_read();      // (the environment as it is at this call)
+  if (conv_check(q)) { out[0] = 2; return 0; }
+  ConvPolicy pol = conv_policy_default();      // odt_config first, the knobs on top (resolve_conv_policy)
+  if (conv_arith == ODT_ARITH_F32) pol.arith = 0;
+  else if (conv_arith == ODT_ARITH_BF16X3) pol.arith = 1;
+  if (conv_split_family >= 1 && conv_split_family <= 3) pol.family = conv_split_family;
+  pol = conv_policy_with_knobs(pol, kn);
+  const ConvChoice ch = conv_select(q, pol, kn);
+  if (conv_variant_row(ch.variant).family != CF_F32) {
+    conv_use_variant(q, ch.variant, ch.splitk, ch.reduce_blocks);
+    q.wt_split = ph_f;
+    if (conv_variant_row(q.variant).family == CF_H2) q.h2_chinv = ph_f;
+    if (conv_split_partial_bytes(q) > 0) q.partial = ph_f;
+  }
+  if (conv_finish(q, kn)) { out[0] = 2; return 0; }
+  const ConvKernelRow& r = conv_variant_row(q.variant);
+  if (name && name_cap > 0) { std::strncpy(name, r.name, name_cap - 1); name[name_cap - 1] = 0; }
+  if (r.family != CF_F32) {
+    out[0] = 1; out[1] = r.family; out[2] = r.bm; out[3] = r.bn; out[4] = (r.flags & CVF_KWR) ? 1 : 0; out[5] = q.splitk;
+    out[6] = (r.flags & CVF_DSTAGE) ? 1 : 0; out[10] = q.reduce_blocks;
+  } else {
+    out[7] = r.bn == 128 ? 3 : (r.bm == 64 ? 2 : 1); out[8] = (r.flags & CVF_ST2) ? 2 : 1; out[9] = (r.flags & CVF_FINE) ? 1 : 0;
+  }
+  return 0;
 }
 
 int odt_op_preprocess(int device, const void* frames, int dtype, int B, int H, int W, int pad_t, int pad_l,
@@ -693,7 +743,7 @@ int odt_op_mbconv_expand_dw(int device, const float* x, int B, int H, int W, int
       g.alloc("out", (size_t)B * Ho * Wo * lmid, &q.out)) return 1;
   {   // the expand weights as the bf16x3 piece image of the one-stage 256 x 64 kernel (plan_effdet.hip, fused MBConv)
     ConvParams cp; std::memset(&cp, 0, sizeof(cp));
-    cp.wt = dew; cp.Cout = mid; cp.Cin = in_ldc; cp.kh = 1; cp.kw = 1; cp.wt_split_kind = 1; cp.wt_split_bn = 64;
+    cp.wt = dew; cp.Cout = mid; cp.Cin = in_ldc; cp.kh = 1; cp.kw = 1; conv_use_variant(cp, CV_SPLIT1_256x64);
     if (conv_make_split_weights(cp, img, nullptr)) return 1;
   }
   q.x = dx; q.B = B; q.H = H; q.W = W; q.in_ldc = in_ldc; q.w_img = img; q.e_bias = deb; q.mid = mid; q.lmid = lmid;

@@ -245,10 +245,12 @@ int attach_split_weights(odt_model* m) {
     ConvOp& c = m->convs[op.conv];
     c.p.in_amax = slot_ptr(c.p.in, tail);
     c.p.in2_amax = slot_ptr(c.p.in2, tail);
-    if (!conv_split_wanted(c.p, pol)) { slot_of.erase(c.p.out); continue; }      // exact-f32 kernel: records no range
-    conv_split_choose(c.p, pol);
+    const ConvChoice ch = conv_select(c.p, pol, m->knobs);
+    const ConvKernelRow& row = conv_variant_row(ch.variant);
+    if (row.family == CF_F32) { slot_of.erase(c.p.out); continue; }      // exact-f32 kernel (conv_finish picks its row): records no range
+    conv_use_variant(c.p, ch.variant, ch.splitk, ch.reduce_blocks);
     const int K = c.p.kh * c.p.kw * c.p.Cin + (c.p.in2 != nullptr ? c.p.Cin2 : 0);
-    const auto key = std::make_pair(c.p.wt, c.p.wt_split_kind * 1024 + c.p.wt_split_bn);
+    const auto key = std::make_pair(c.p.wt, row.family * 1024 + row.bn);      // (the weight image's layout)
     auto it = made.find(key);
     if (it == made.end()) {
       float* img = m->alloc_f((conv_split_weight_bytes(c.p.Cout, K) + 3) / 4, false);
@@ -270,7 +272,7 @@ int attach_split_weights(odt_model* m) {
       const bool per_wave = m->knobs.get(K_AMAX_PER_WAVE).c0 == '1';
       if (per_wave) c.p.debug |= 0x4000;      // A/B: range record per wave instead of per workgroup
     }
-    if (c.p.wt_split_kind == 2) {
+    if (row.family == CF_H2) {
       c.p.h2_chinv = conv_h2_chinv(c.p.wt_split, c.p.Cout, K); ++m->convs_h2;
       const bool norot = m->knobs.off(K_CONV_H2_ROT);
       if (norot) c.p.debug |= 0x100;          // A/B: every workgroup walks the K slices in the same order
@@ -338,7 +340,8 @@ int fuse_rpn_heads(odt_model* m) {
     if (a.name.compare(0, 10, "rpn/conv0@") != 0 || b.name.compare(0, 9, "rpn/head@") != 0) continue;
     const ConvParams& bp = b.p;
     ConvParams& ap = a.p;
-    const bool ok = ap.wt_split != nullptr && (ap.wt_split_kind == 3 || ap.wt_split_kind == 2) && ap.wt_split_bn == 256 && ap.Cout == 256 && ap.splitk <= 1 &&
+    const ConvKernelRow& ar = conv_variant_row(ap.variant);
+    const bool ok = ap.wt_split != nullptr && (ar.family == CF_SPLIT3 || ar.family == CF_H2) && ar.bn == 256 && ap.Cout == 256 && ap.splitk <= 1 &&
                     ap.res_mode == 0 && ap.in2 == nullptr && ap.relu <= 1 && bp.in == ap.out && bp.kh == 1 && bp.kw == 1 &&
                     bp.Cin == 256 && bp.Cout == 15 && bp.out_ldc == 16 && bp.stride == 1 && bp.res_mode == 0 && bp.relu == 0 &&
                     bp.out_oy == 0 && bp.out_ox == 0 && bp.out_H == bp.Ho && bp.out_W == bp.Wo && bp.Ho == ap.Ho && bp.Wo == ap.Wo &&
@@ -380,10 +383,7 @@ int fuse_bottleneck_tails(odt_model* m) {
     if (oa.kind != OP_CONV || ob.kind != OP_CONV || oa.skip || ob.skip) continue;
     ConvOp& a = m->convs[oa.conv]; ConvOp& b = m->convs[ob.conv];
     if (a.p.Cout < min_cout) continue;
-    // (a 64-wide conv2 on the kw-reuse kernel's 512 x 64 tiles: the fused tail works on 256-row tiles -- same weight image)
-    const int bm0 = a.p.wt_split_bm;
-    if (a.p.Cout == 64 && a.p.wt_split_kind == 2 && a.p.wt_split_kwr == 1 && bm0 == 512) a.p.wt_split_bm = 256;
-    if (!conv_h2f_fusable(a.p, b.p)) { a.p.wt_split_bm = bm0; continue; }
+    if (!conv_h2f_fusable(a.p, b.p)) continue;
     // nothing else may read conv2's output (taps: a keep_taps handle exposes no stage tensor under this name, see add_conv)
     bool other = false;
     for (size_t k = 0; k < m->ops.size() && !other; ++k) {
@@ -391,7 +391,7 @@ int fuse_bottleneck_tails(odt_model* m) {
       visit_op_ptrs(m, k, [&](auto& ptr) { if ((const void*)ptr == (const void*)a.p.out) other = true; });
     }
     for (const auto& kv : m->taps) if (kv.second.d == a.p.out) other = true;
-    if (other) { a.p.wt_split_bm = bm0; continue; }
+    if (other) continue;
     const int K = b.p.Cin;
     auto it = made.find(b.p.wt);
     if (it == made.end()) {
@@ -401,6 +401,7 @@ int fuse_bottleneck_tails(odt_model* m) {
       it = made.emplace(b.p.wt, img).first;
     }
     ConvParams& ap = a.p;
+    conv_use_variant(ap, conv_variant_fused_tail(ap.variant), ap.splitk, ap.reduce_blocks);
     ap.f_wt = it->second; ap.f_chinv = conv_h2f_chinv(it->second, b.p.Cout, K); ap.f_bias = b.p.bias;
     ap.f_res = b.p.res_mode != 0 ? b.p.res : nullptr; ap.f_res_ldc = b.p.res_ldc;
     ap.f_out = b.p.out; ap.f_out_ldc = b.p.out_ldc; ap.f_cout = b.p.Cout; ap.f_relu = b.p.relu; ap.f_out_amax = b.p.out_amax;
@@ -440,7 +441,8 @@ int fuse_stem(odt_model* m) {
     if (other) continue;
     // the conv map no longer exists: an arena handle must neither reserve memory for its stage name nor hand it out
     for (auto it = m->taps.begin(); it != m->taps.end();) { if (it->second.d == ap.out) it = m->taps.erase(it); else ++it; }
-    ap.out = ob.out.d; ap.out_H = ob.out.H; ap.out_W = ob.out.W; ap.out_ldc = ob.out.C; ap.stem_pool = 1;
+    ap.out = ob.out.d; ap.out_H = ob.out.H; ap.out_W = ob.out.W; ap.out_ldc = ob.out.C;
+    conv_use_variant(ap, CV_H2_STEM, ap.splitk, ap.reduce_blocks);
     if (m->knobs.get(K_STEM_GRID).set) ap.debug |= ((int)m->knobs.get(K_STEM_GRID).i & 0x3ff) << 20;   // test knob: workgroups of the launch
     ob.skip = true;
     m->stem_fused = 1;

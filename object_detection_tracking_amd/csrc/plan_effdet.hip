@@ -259,8 +259,8 @@ int build_effdet_heads(odt_model* m, const Tensor* red, const int* red_ch) {
     q.B = 1; q.H = Mtot / 256; q.W = 256; q.in_Ha = q.H; q.in_Wa = 256; q.Cin = LF; q.in_ldc = LF; q.Ho = q.H; q.Wo = 256; q.Cout = F;
     q.kh = q.kw = 1; q.stride = 1; q.dil = 1; q.out_H = q.H; q.out_W = 256; q.out_ldc = LF;
     const ConvPolicy pol = resolve_conv_policy(m);
-    merge = conv_split_wanted(q, pol);
-    if (merge) { conv_split_choose(q, pol); merge = q.wt_split_kind == 3 && q.splitk <= 1; }
+    const ConvChoice ch = conv_select(q, pol, m->knobs);
+    merge = conv_variant_row(ch.variant).family == CF_SPLIT3 && ch.splitk <= 1;
   }
   if (merge) {
     auto level_view = [&](const Tensor& cat, int l) {
@@ -501,7 +501,7 @@ int build_plan_effnet(odt_model* m) {
           float* img = m->alloc_f((mbconv_expand_weight_bytes(lmid, x.C) + 3) / 4, false);
           ODT_CHECK(img != nullptr, "device allocation failed (expand weight image of " + p + ")");
           ConvParams cp{};
-          cp.wt = ewt; cp.Cout = mid; cp.Cin = x.C; cp.kh = 1; cp.kw = 1; cp.wt_split_kind = 1; cp.wt_split_bn = 64;
+          cp.wt = ewt; cp.Cout = mid; cp.Cin = x.C; cp.kh = 1; cp.kw = 1; conv_use_variant(cp, CV_SPLIT1_256x64);
           if (conv_make_split_weights(cp, img, nullptr)) return 1;
           ODT_HIP(hipDeviceSynchronize());
           q.w_img = img;

@@ -677,8 +677,9 @@ int odt_profile_layer(odt_handle h, int index, char* name, int name_cap, double*
   const ConvOp& c = h->convs[index];
   if (name && name_cap > 0) {    // layers on the bf16x3 split kernel are tagged (bench.py / profile_layers.py group by it)
     const bool fused = index < (int)h->conv_fused.size() && h->conv_fused[index];
-    const std::string nm = c.name + (fused ? "[fused into the producer's epilogue]" : (c.p.head_wt != nullptr ? "+head" : (c.p.f_wt != nullptr ? "+conv3" : (c.p.stem_pool ? "+pool0" : "")))) +
-                           (!fused && c.p.wt_split != nullptr ? (c.p.wt_split_kind == 2 ? "[fp16x2]" : "[bf16x3]") : "");
+    const ConvKernelRow& row = conv_variant_row(c.p.variant);
+    const std::string nm = c.name + (fused ? "[fused into the producer's epilogue]" : (c.p.head_wt != nullptr ? "+head" : ((row.flags & CVF_FTAIL) ? "+conv3" : ((row.flags & CVF_STEM) ? "+pool0" : "")))) +
+                           (!fused && c.p.wt_split != nullptr ? (row.family == CF_H2 ? "[fp16x2]" : "[bf16x3]") : "");
     std::strncpy(name, nm.c_str(), name_cap - 1); name[name_cap - 1] = 0;
   }
   if (flops) *flops = (index < (int)h->conv_fused.size() && h->conv_fused[index]) ? 0.0 : conv_flops(c.p);
@@ -693,7 +694,7 @@ int odt_describe(odt_handle h, char* buf, int cap) {
   for (size_t i = 0; i < h->convs.size(); ++i) {
     const ConvOp& c = h->convs[i];
     if (i < h->conv_fused.size() && h->conv_fused[i]) { ++nfused; continue; }
-    fam[c.p.wt_split != nullptr ? c.p.wt_split_kind : 0] += 1;
+    fam[c.p.wt_split != nullptr ? conv_variant_row(c.p.variant).family : CF_F32] += 1;
     if (c.p.wt_split != nullptr && c.p.splitk > 1) ++nsk;
   }
   size_t dev_bytes = 0;

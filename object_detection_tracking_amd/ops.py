@@ -84,6 +84,24 @@ def stem(frame_pad, w_hwio, bias, fuse=True, grid=0, lib=None, device=0):
   return out
 
 
+CONV_CHOICE_SHAPE = ("B", "H", "W", "Cin", "Cout", "kh", "kw", "stride", "dil", "pad", "Ho", "Wo", "in_Wa", "Cin2", "res_mode", "ranges",
+                     "in_ldc", "out_ldc")
+CONV_CHOICE_OUT = ("status", "kind", "bm", "bn", "kwr", "splitk", "dstage", "f32_tile", "f32_stages", "f32_fine", "reduce_blocks")
+
+
+def conv_choice(shape, conv_arith=0, conv_split_family=0, lib=None):
+  """odt_op_conv_choice: the kernel the library would run this conv on (host only; the ODT_* knobs are read at the call).
+  shape: the CONV_CHOICE_SHAPE values; returns the CONV_CHOICE_OUT fields and the row's name as a dict."""
+  lib = lib if lib is not None else _lib.OdtLib(_lib.LIB_HIP_PATH)      # (no device needed: not get_lib())
+  s = i32(list(shape)); out = np.zeros(len(CONV_CHOICE_OUT), np.int32)
+  assert s.shape == (len(CONV_CHOICE_SHAPE),)
+  name = C.create_string_buffer(64)
+  lib.check(lib.dll.odt_op_conv_choice(iptr(s), int(conv_arith), int(conv_split_family), iptr(out), name, 64))
+  d = dict(zip(CONV_CHOICE_OUT, (int(v) for v in out)))
+  d["name"] = name.value.decode()
+  return d
+
+
 def preprocess(frames, pad_t, pad_l, Hp, Wp, lib=None, device=0):
   """reference models.py:340-355 + zero pad; returns [B,Hp,Wp,4]."""
   lib = _L(lib)

@@ -543,7 +543,7 @@ SPLIT_CASES = [
 ]
 
 
-# kernel families of the split path (conv_split_choose): "3/256", "3/128": conv_split3_kernel (8 waves, LDS-DMA weight
+# kernel families of the split path (conv_select): "3/256", "3/128": conv_split3_kernel (8 waves, LDS-DMA weight
 # stages, three-stage ring; the default) with 256- / 128-row tiles; "1": the one-stage BK = 32 loop (the 64-wide layers)
 # "3/128/k3": the same with the reduction cut into three split-K ranges + split_reduce_kernel
 # "3/256/nokwr": 256-row tiles with the kw-reuse kernel (conv_split3k_kernel, the default for stride-1 KH x 3 convs) off
