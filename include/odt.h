@@ -101,6 +101,9 @@ typedef struct odt_config {
                              * of forward i + 1 (one handle, forwards back to back: +1 %); -1: the whole forward stays on the compute
                              * stream -- for handles that run consecutive frames side by side (models.predict_stream: with three b = 1
                              * frames in flight 189 FPS with the side streams, 235 without: they compete for hardware queues) */
+  int32_t use_se;           /* model version 6: squeeze-excitation in every ResNet bottleneck (nn.py:506-517; variables
+                             * groupG/blockI/fc1/{W,b}, fc2/{W,b}, W as [in, out]): l * sigmoid(fc2(relu(fc1(mean_HW(l))))) between
+                             * conv3 + BN and the residual add */
 } odt_config;
 
 /* conv_arith: all modes keep f32 tensors and f32 accumulation.  ODT_ARITH_F32: every product on the exact-f32 MFMA
@@ -451,6 +454,21 @@ int odt_op_dwconv(int device, const float* in, int B, int H, int W, int ldc, con
  * channel-sum pixel splits. */
 int odt_op_se_gate(int device, const float* x, int B, int HW, int ldc, int mid, int se, const float* w1, const float* b1,
                    const float* w2t, const float* b2, float* mean, float* gate, float* scaled, int32_t* info);
+/* SE-ResNet bottleneck (model version 6, nn.py:506-517; csrc/resnet_se.hip), each as the plan runs it.
+ * odt_op_rse_gate: spatial mean of t2 [B,HW,ch] (ch % 4 == 0) -> relu(mean . w1 + b1) (w1 [r][ch], b1 [r]) -> sigmoid(. w2t + b2)
+ * (w2t [r][cout], b2 [cout]) -> mean [B,ch], gate [B,cout].
+ * odt_op_rse_apply: out = max(y * gate[b, c] + shortcut, 0) over the first C channels of [B,HW,ldc] tensors (ldc % 4 == 0, gate
+ * [B,ldc]); channels [C, ldc) of out come back as they went in; in_place: the kernel writes over y.  amax [1]: the |max| the
+ * kernel recorded for out.
+ * odt_op_se_tail: t2 [B,H,W,ch] (ch % 32 == 0) -> gate (w1 / b1: conv3 + BN folded into fc1 by the caller) -> conv3 (w3 [ch, 4 ch]
+ * with BN folded, + b3, no residual, no ReLU) -> apply with shortcut [B,H,W,4 ch] -> out [B,H,W,4 ch], gate [B,4 ch], amax [1]. */
+int odt_op_rse_gate(int device, const float* t2, int B, int HW, int ch, int r, int cout, const float* w1, const float* b1,
+                    const float* w2t, const float* b2, float* mean, float* gate);
+int odt_op_rse_apply(int device, const float* y, const float* gate, const float* shortcut, int B, int HW, int C, int ldc,
+                     int in_place, float* out, float* amax);
+int odt_op_se_tail(int device, const float* t2, int B, int H, int W, int ch, const float* w3, const float* b3, const float* w1,
+                   const float* b1, const float* w2t, const float* b2, const float* shortcut, float* out, float* gate,
+                   float* amax);
 /* BiFPN node input fusion (launch_bifpn_fuse): n = 1..3 inputs ins[k] [B,in_hw[k][0],in_hw[k][1],ldc], mode[k] 0 same
  * size, 1 nearest resize, 2 3x3 / s2 'SAME' max pool with pads[k] = (top, left); wsm != NULL: 'fastattn' with the raw
  * WSM scalars [n], else a plain sum; act 0 / 2 (swish).  out [B,h,w,ldc]. */

@@ -71,6 +71,8 @@ def make_config(**overrides):
   c.keep_taps = False             # True: dedicated buffers for every stage tensor (engine.tap() of backbone stages; ~5x the activation memory)
   for k, v in overrides.items():
     setattr(c, k, v)
+  if c.version == 6 and "use_dilations" not in overrides:
+    c.use_dilations = False       # --version 6 sets use_se and no dilations (obj_detect_tracking.py:278-280)
   return finalize_config(c)
 
 

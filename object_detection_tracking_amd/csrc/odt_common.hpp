@@ -366,6 +366,35 @@ int launch_se_gate(const float* in, const SeGateParams& p, int B, float* scratch
 // the gate from the depthwise kernel's fused partial sums (p.part / p.nsplit set by the caller): fold + reduce + expand
 int launch_se_gate_from_parts(const SeGateParams& p, int B, hipStream_t stream);
 
+// ------------------------------------------------------- SE-ResNet bottleneck (resnet_se.hip; reference nn.py:506-517)
+// gate[b, :] = sigmoid(relu(mean_HW(t2)[b, :] . w1 + b1) . w2 + b2) with conv3 + BN folded into w1 / b1 on the host (the
+// spatial mean commutes with the 1x1 conv and the affine BN), then out = max(y * gate[b, c] + shortcut, 0).
+struct ResSeParams {
+  const float* t2;     // [B,HW,ch] conv2's output (dense)
+  int B, HW, ch, r, cout;   // r = ch / 4 reduced channels, cout = 4 ch
+  const float* w1;     // [r][ch]    (conv3 . bnscale) @ fc1/W, transposed
+  const float* b1;     // [r]        bnshift @ fc1/W + fc1/b
+  const float* w2t;    // [r][cout]  fc2/W
+  const float* b2;     // [cout]
+  float* part;         // scratch [B][channel_mean_splits(HW, ch, B)][ch]
+  float* mean;         // [B][ch]
+  float* rvec;         // [B][r]
+  float* gate;         // [B][gate_ld]
+  int gate_ld;         // row stride of gate (>= cout, multiple of 4)
+};
+int launch_resnet_se_gate(const ResSeParams& p, hipStream_t stream);
+// the gate MLP alone, from p.mean
+int launch_resnet_se_mlp(const ResSeParams& p, hipStream_t stream);
+struct ResSeApplyParams {
+  const float* y;      // [B,HW,ldc] conv3 + BN
+  const float* sc;     // [B,HW,ldc] shortcut
+  const float* gate;   // [B][gate_ld]
+  float* out;          // [B,HW,ldc]; may be y.  Channels [C, ldc) are never written
+  unsigned* amax;      // range slot of out (|max| of what is stored) or nullptr
+  int B, HW, C, ldc, gate_ld;   // ldc, gate_ld multiples of 4
+};
+int launch_resnet_se_apply(const ResSeApplyParams& p, hipStream_t stream);
+
 // ------------------------------------------------------- EfficientDet tail (effdet_post.hip)
 struct EffPostParams {
   const float* cls[5];     // per level [B, npix, ldc_cls]  (9 * ncls valid channels: anchor-major)

@@ -60,7 +60,7 @@ struct ConvOp {
 
 enum OpKind { OP_PRE, OP_CONV, OP_POOL, OP_SUB2, OP_PROPOSALS, OP_ROI_HEAD, OP_DETECT, OP_ROI_FINAL,
               OP_ROI_MASK, OP_MASK_SELECT, OP_PRE_RGB, OP_DW, OP_CMEAN, OP_CSCALE, OP_FUSE, OP_EFF_POST, OP_ROI_EFF, OP_SE_GATE,
-              OP_SE_GATE_MEAN, OP_WSCALE, OP_MB_EXPAND_DW };
+              OP_SE_GATE_MEAN, OP_WSCALE, OP_MB_EXPAND_DW, OP_RSE_GATE, OP_RSE_APPLY };
 struct Op {
   OpKind kind;
   int conv = -1;        // index into convs
@@ -69,6 +69,8 @@ struct Op {
   MbExpandDwParams mb{};   // OP_MB_EXPAND_DW
   FuseParams fuse{};    // OP_FUSE
   SeGateParams se{};    // OP_SE_GATE (aux2 = partial-sum scratch)
+  ResSeParams rse{};    // OP_RSE_GATE: pool of conv2's output + the SE-ResNet gate
+  ResSeApplyParams rsa{};   // OP_RSE_APPLY: gate * conv3 + shortcut, ReLU
   float* aux = nullptr; // OP_CMEAN: means out [B,ldc]; OP_CSCALE / OP_WSCALE: gates in [B,ldc]
   const float* wt0 = nullptr;   // OP_WSCALE: the conv's unscaled weights [Cout][K] (conv = index of the conv whose weights are rebuilt)
   float* aux2 = nullptr;   // OP_CMEAN: partial-sum scratch
@@ -124,6 +126,7 @@ struct odt_model {
   // [M,C,7,7] features): set by odt_submit_ex for the duration of run_plan
   Slot* d2h_slot = nullptr; int d2h_want = 0;
   ConvPolicy policy{};               // conv arithmetic / kernel-family policy of this handle (attach_split_weights)
+  int se_blocks = 0;                 // SE-ResNet (odt_config.use_se): bottlenecks that run pool + gate + apply (resnet_se.hip)
   int mb_fused = 0;                  // EfficientNet: MBConv blocks whose expand + depthwise run as one kernel (effnet_mbconv.hip)
   // tail overlap: the selection / ROIAlign / box-head / NMS kernels of forward i (a few dozen workgroups each,
   // ~2 ms per 8-frame step) run on a side stream under the backbone of forward i+1.  The next forward's FPN stage
@@ -213,6 +216,8 @@ int upload_conv(odt_model* m, const std::string& scope, int kh, int kw, int cin,
 int upload_conv_cat(odt_model* m, const std::string& sa, int cin_a, const std::string& sb, int cin_b, int cout,
                     const float** wt_out, const float** bias_out);
 int upload_raw(odt_model* m, const std::vector<float>& v, const float** out);
+int upload_se_gate(odt_model* m, const std::string& pre, int ch, const float** w1, const float** b1, const float** w2t,
+                   const float** b2);
 int add_conv(odt_model* m, const std::string& name, const Tensor& in, int cin, const float* wt, const float* bias, int kh,
              int kw, int cout, int stride, int dil, int pad_t, int pad_l, int Ho, int Wo, int oy, int ox, const Tensor* res,
              int res_mode, bool relu, int out_ldc, Tensor* out, const std::string& tap);
@@ -261,6 +266,8 @@ void visit_op_ptrs(odt_model* m, size_t oi, F&& f) {
     case OP_MASK_SELECT: f(m->mask_sel.logits); break;
     case OP_DW: f(op.dw.in); f(op.dw.out); for (auto& p : op.dw.lin) f(p); for (auto& p : op.dw.lout) f(p); break;
     case OP_MB_EXPAND_DW: f(op.mb.x); f(op.mb.out); break;
+    case OP_RSE_GATE: f(op.rse.t2); f(op.rse.part); f(op.rse.mean); f(op.rse.rvec); f(op.rse.gate); break;
+    case OP_RSE_APPLY: f(op.rsa.y); f(op.rsa.sc); f(op.rsa.gate); f(op.rsa.out); break;
     case OP_FUSE: for (auto& p : op.fuse.in) f(p); f(op.fuse.out); break;
     case OP_EFF_POST: for (auto& p : m->eff_post.cls) f(p); for (auto& p : m->eff_post.box) f(p); break;
     case OP_CMEAN: case OP_CSCALE: case OP_SE_GATE: case OP_SE_GATE_MEAN: case OP_WSCALE: case OP_POOL: case OP_SUB2: break;

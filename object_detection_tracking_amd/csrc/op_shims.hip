@@ -762,6 +762,108 @@ int odt_op_mbconv_expand_dw(int device, const float* x, int B, int H, int W, int
   return 0;
 }
 
+// ---- SE-ResNet bottleneck (resnet_se.hip) ----------------------------------------------------------------------------
+namespace {
+
+// device copies of the gate's weights + its scratch, as the plan lays them out (gate rows zero-initialised)
+int rse_gate_bufs(GBufs& g, ResSeParams& gp, int B, int HW, int ch, int r, int cout, const float* w1, const float* b1,
+                  const float* w2t, const float* b2) {
+  std::memset(&gp, 0, sizeof(gp));
+  gp.B = B; gp.HW = HW; gp.ch = ch; gp.r = r; gp.cout = cout; gp.gate_ld = (cout + 3) / 4 * 4;
+  float *dw1, *db1, *dw2, *db2;
+  if (g.alloc("rse_w1", (size_t)r * ch, &dw1, -1, w1) || g.alloc("rse_b1", (size_t)r, &db1, -1, b1) ||
+      g.alloc("rse_w2t", (size_t)r * cout, &dw2, -1, w2t) || g.alloc("rse_b2", (size_t)cout, &db2, -1, b2) ||
+      g.alloc("rse_part", (size_t)B * channel_mean_splits(HW, ch, B) * ch, &gp.part) ||
+      g.alloc("rse_mean", (size_t)B * ch, &gp.mean) || g.alloc("rse_rvec", (size_t)B * r, &gp.rvec) ||
+      g.alloc("rse_gate", (size_t)B * gp.gate_ld, &gp.gate, 0)) return 1;
+  gp.w1 = dw1; gp.b1 = db1; gp.w2t = dw2; gp.b2 = db2;
+  return 0;
+}
+
+int rse_read_amax(const unsigned* slot, float* amax) {
+  unsigned bits[kAmaxWays], a = 0u;
+  ODT_HIP(hipMemcpy(bits, slot, sizeof(bits), hipMemcpyDeviceToHost));
+  for (unsigned b : bits) a = b > a ? b : a;
+  std::memcpy(amax, &a, 4);
+  return 0;
+}
+
+}  // namespace
+
+int odt_op_rse_gate(int device, const float* t2, int B, int HW, int ch, int r, int cout, const float* w1, const float* b1,
+                    const float* w2t, const float* b2, float* mean, float* gate) {
+  ODT_CHECK(t2 && w1 && b1 && w2t && b2 && mean && gate, "odt_op_rse_gate: null argument");
+  ODT_CHECK(B >= 1 && HW >= 1 && ch >= 4 && ch % 4 == 0 && r >= 1 && cout >= 1, "odt_op_rse_gate: bad sizes");
+  if (set_dev(device)) return 1;
+  GBufs g;
+  ResSeParams gp;
+  float* dt2;
+  if (g.alloc("t2", (size_t)B * HW * ch, &dt2, -1, t2) || rse_gate_bufs(g, gp, B, HW, ch, r, cout, w1, b1, w2t, b2)) return 1;
+  gp.t2 = dt2;
+  if (launch_resnet_se_gate(gp, nullptr)) return 1;
+  if (g.check("odt_op_rse_gate")) return 1;
+  if (get_dev(mean, gp.mean, (size_t)B * ch)) return 1;
+  for (int b = 0; b < B; ++b)
+    if (get_dev(gate + (size_t)b * cout, gp.gate + (size_t)b * gp.gate_ld, (size_t)cout)) return 1;
+  return 0;
+}
+
+int odt_op_rse_apply(int device, const float* y, const float* gate, const float* shortcut, int B, int HW, int C, int ldc,
+                     int in_place, float* out, float* amax) {
+  ODT_CHECK(y && gate && shortcut && out && amax, "odt_op_rse_apply: null argument");
+  ODT_CHECK(B >= 1 && HW >= 1 && C >= 1 && ldc >= C && ldc % 4 == 0, "odt_op_rse_apply: bad sizes");
+  if (set_dev(device)) return 1;
+  GBufs g;
+  ResSeApplyParams ap; std::memset(&ap, 0, sizeof(ap));
+  const size_t n = (size_t)B * HW * ldc;
+  float *dy, *ds, *dg, *dout;
+  unsigned* slot;
+  // (gate [B, ldc]; out starts as a copy of the caller's buffer: the channels [C, ldc) must come back as they went in)
+  if (g.alloc("y", n, &dy, -1, y) || g.alloc("shortcut", n, &ds, -1, shortcut) || g.alloc("gate", (size_t)B * ldc, &dg, -1, gate) ||
+      g.alloc("out", n, &dout, -1, out) || g.alloc("range slot", (size_t)kAmaxWays, &slot, 0)) return 1;
+  ap.y = dy; ap.sc = ds; ap.gate = dg; ap.out = in_place ? dy : dout; ap.amax = slot;
+  ap.B = B; ap.HW = HW; ap.C = C; ap.ldc = ldc; ap.gate_ld = ldc;
+  if (launch_resnet_se_apply(ap, nullptr)) return 1;
+  if (g.check("odt_op_rse_apply")) return 1;
+  if (rse_read_amax(slot, amax)) return 1;
+  return get_dev(out, ap.out, n);
+}
+
+int odt_op_se_tail(int device, const float* t2, int B, int H, int W, int ch, const float* w3, const float* b3, const float* w1,
+                   const float* b1, const float* w2t, const float* b2, const float* shortcut, float* out, float* gate,
+                   float* amax) {
+  ODT_CHECK(t2 && w3 && b3 && w1 && b1 && w2t && b2 && shortcut && out && gate && amax, "odt_op_se_tail: null argument");
+  ODT_CHECK(B >= 1 && H >= 1 && W >= 1 && ch >= 32 && ch % 32 == 0, "odt_op_se_tail: ch must be a multiple of 32");
+  if (set_dev(device)) return 1;
+  const int C3 = ch * 4, r = ch / 4, HW = H * W;
+  const size_t M = (size_t)B * HW;
+  std::vector<float> w3t((size_t)C3 * ch);
+  for (int i = 0; i < ch; ++i) for (int o = 0; o < C3; ++o) w3t[(size_t)o * ch + i] = w3[(size_t)i * C3 + o];
+  GBufs g;
+  ResSeParams gp;
+  float *dt2, *dw3, *db3, *ds, *dy, *dout;
+  unsigned* slot;
+  if (g.alloc("t2", M * ch, &dt2, -1, t2) || g.alloc("w3", w3t.size(), &dw3, -1, w3t.data()) || g.alloc("b3", (size_t)C3, &db3, -1, b3) ||
+      g.alloc("shortcut", M * C3, &ds, -1, shortcut) || g.alloc("y", M * C3, &dy) || g.alloc("out", M * C3, &dout) ||
+      g.alloc("range slot", (size_t)kAmaxWays, &slot, 0) || rse_gate_bufs(g, gp, B, HW, ch, r, C3, w1, b1, w2t, b2)) return 1;
+  gp.t2 = dt2;
+  // the plan's order: pool + gate, conv3 (BN folded, no residual, no ReLU), apply
+  if (launch_resnet_se_gate(gp, nullptr)) return 1;
+  ConvParams p; std::memset(&p, 0, sizeof(p));
+  p.in = dt2; p.wt = dw3; p.bias = db3; p.out = dy;
+  p.B = B; p.H = H; p.W = W; p.Cin = ch; p.in_ldc = ch; p.in_Ha = H; p.in_Wa = W; p.Ho = H; p.Wo = W; p.Cout = C3;
+  p.kh = 1; p.kw = 1; p.stride = 1; p.dil = 1; p.out_H = H; p.out_W = W; p.out_ldc = C3;
+  if (run_conv(p, knobs_read())) return 1;
+  ResSeApplyParams ap; std::memset(&ap, 0, sizeof(ap));
+  ap.y = dy; ap.sc = ds; ap.gate = gp.gate; ap.out = dout; ap.amax = slot;
+  ap.B = B; ap.HW = HW; ap.C = C3; ap.ldc = C3; ap.gate_ld = gp.gate_ld;
+  if (launch_resnet_se_apply(ap, nullptr)) return 1;
+  if (g.check("odt_op_se_tail")) return 1;
+  if (rse_read_amax(slot, amax)) return 1;
+  if (get_dev(gate, gp.gate, (size_t)B * C3)) return 1;
+  return get_dev(out, dout, M * C3);
+}
+
 int odt_op_effdet_post(int device, int B, int ncls, const int32_t* npix, int ldc_cls, int ldc_box,
                        const float* const* cls, const float* const* box, const float* anchors, int k, int max_out,
                        float score_thresh, float iou_thresh, float image_scale, int32_t* cand_idx, float* cand_boxes,

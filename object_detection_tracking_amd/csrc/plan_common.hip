@@ -115,6 +115,49 @@ int upload_conv_cat(odt_model* m, const std::string& sa, int cin_a, const std::s
   return 0;
 }
 
+// The SE gate of bottleneck `pre` (reference nn.py:506-517) with conv3 + BN folded into fc1.  conv3 is 1x1 and BN affine, so
+// mean_HW(BN(conv3(t2))) = BN(conv3(mean_HW(t2))):
+//   w1[j][i] = sum_o conv3/W[i][o] * bnscale[o] * fc1/W[o][j]      b1[j] = sum_o bnshift[o] * fc1/W[o][j] + fc1/b[j]
+// in double, rounded to f32 once; w2t = fc2/W as it is ([in, out] = [r][4 ch]).
+int upload_se_gate(odt_model* m, const std::string& pre, int ch, const float** w1, const float** b1, const float** w2t,
+                   const float** b2) {
+  const int C4 = ch * 4, r = ch / 4;
+  const HostTensor* W3 = find_w(m, pre + "/conv3/W");
+  const HostTensor* g = find_w(m, pre + "/conv3/bn/gamma");
+  const HostTensor* be = find_w(m, pre + "/conv3/bn/beta");
+  const HostTensor* mu = find_w(m, pre + "/conv3/bn/mean/EMA");
+  const HostTensor* var = find_w(m, pre + "/conv3/bn/variance/EMA");
+  const HostTensor* f1 = find_w(m, pre + "/fc1/W");
+  const HostTensor* f1b = find_w(m, pre + "/fc1/b");
+  const HostTensor* f2 = find_w(m, pre + "/fc2/W");
+  const HostTensor* f2b = find_w(m, pre + "/fc2/b");
+  ODT_CHECK(W3 && g && be && mu && var, "missing conv3 variables for the SE gate of " + pre);
+  ODT_CHECK(f1 && f1b && f2 && f2b, "missing squeeze-excitation variables " + pre + "/fc1, fc2");
+  ODT_CHECK(W3->data.size() == (size_t)ch * C4 && g->data.size() == (size_t)C4 && be->data.size() == (size_t)C4 &&
+            mu->data.size() == (size_t)C4 && var->data.size() == (size_t)C4, "bad conv3 shapes for the SE gate of " + pre);
+  ODT_CHECK(f1->data.size() == (size_t)C4 * r && f1b->data.size() == (size_t)r && f2->data.size() == (size_t)r * C4 &&
+            f2b->data.size() == (size_t)C4, "bad squeeze-excitation shapes in " + pre);
+  std::vector<double> scale(C4), acc(r);
+  std::vector<float> v1((size_t)r * ch), vb(r);
+  for (int j = 0; j < r; ++j) acc[j] = (double)f1b->data[j];
+  for (int o = 0; o < C4; ++o) {
+    scale[o] = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5);
+    const double shift = (double)be->data[o] - (double)mu->data[o] * scale[o];
+    for (int j = 0; j < r; ++j) acc[j] += shift * (double)f1->data[(size_t)o * r + j];
+  }
+  for (int j = 0; j < r; ++j) vb[j] = (float)acc[j];
+  for (int i = 0; i < ch; ++i) {
+    std::fill(acc.begin(), acc.end(), 0.0);
+    for (int o = 0; o < C4; ++o) {
+      const double a = (double)W3->data[(size_t)i * C4 + o] * scale[o];
+      const float* f = &f1->data[(size_t)o * r];
+      for (int j = 0; j < r; ++j) acc[j] += a * (double)f[j];
+    }
+    for (int j = 0; j < r; ++j) v1[(size_t)j * ch + i] = (float)acc[j];
+  }
+  return upload_raw(m, v1, w1) || upload_raw(m, vb, b1) || upload_raw(m, f2->data, w2t) || upload_raw(m, f2b->data, b2);
+}
+
 int upload_raw(odt_model* m, const std::vector<float>& v, const float** out) {
   float* d = m->alloc_f(v.size(), false);
   ODT_CHECK(d != nullptr, "device allocation failed");
@@ -234,6 +277,21 @@ int attach_split_weights(odt_model* m) {
       slot_of[m->roi_head.out_nhwc] = slot;
       m->roi_head.amax = m->amax_dev + (size_t)slot * kAmaxWays;
       m->range_slot_name[slot] = "roi_feat";
+      continue;
+    }
+    if (op.kind == OP_RSE_APPLY) {
+      // the SE block's output: the apply kernel records its range as a conv epilogue would, so that the next block's conv1 /
+      // convshortcut (and the FPN lateral) keep the fp16x2 kernels
+      slot_of.erase(op.rsa.out);
+      if (pol.family != 2) continue;
+      const int g = tail ? 1 : 0;
+      ODT_CHECK(m->amax_used[g] < odt_model::kAmaxSlots, "too many conv outputs for the range slots");
+      const int slot = (tail ? odt_model::kAmaxSlots : 0) + m->amax_used[g]++;
+      slot_of[op.rsa.out] = slot;
+      m->ops[oi].rsa.amax = m->amax_dev + (size_t)slot * kAmaxWays;
+      for (const auto& kv : m->taps)
+        if (kv.second.d == op.rsa.out) m->range_slot_name[slot] = kv.first + " (SE apply)";
+      if (m->range_slot_name[slot].empty()) m->range_slot_name[slot] = "SE block output";
       continue;
     }
     if (op.kind == OP_POOL || op.kind == OP_SUB2) {
@@ -377,6 +435,8 @@ int fuse_bottleneck_tails(odt_model* m) {
   if (e0 == '0') return 0;
   const int min_cout = e0 == '1' ? 256 : (e0 == '2' ? 128 : 64);
   if (m->policy.arith == 0 || m->policy.family != 2) return 0;
+  // SE blocks stay as they are: the fused tail never materialises conv2's output, which the gate pools, and its epilogue has no gate
+  if (m->cfg.use_se) return 0;
   std::map<const float*, const void*> made;
   for (size_t oi = 0; oi + 1 < m->ops.size(); ++oi) {
     Op& oa = m->ops[oi]; Op& ob = m->ops[oi + 1];

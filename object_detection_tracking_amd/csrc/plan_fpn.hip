@@ -87,7 +87,8 @@ int build_plan(odt_model* m) {
       }
       const std::string tap = (i == cnt - 1) ? "c" + std::to_string(g + 2) : (i == 0 ? pre : "");
       const bool fuse_shortcut = !m->knobs.off(K_FUSE_SHORTCUT);
-      if (cin != ch * 4 && fuse_shortcut) {
+      // (SE blocks gate conv3's output but not the shortcut: the two cannot share one GEMM)
+      if (cin != ch * 4 && fuse_shortcut && !cfg.use_se) {
         // stage entry: conv3(t2) + convshortcut(x[::stride]) as one K-concatenated GEMM -- saves the
         // shortcut tensor's write + read and one launch (shortcut[:, :, :-1, :-1] of nn.py:555-556
         // never matters: the stride-2 samples stop at 2 * (Ho - 1) <= h - 2)
@@ -119,6 +120,38 @@ int build_plan(odt_model* m) {
                        0, nullptr, 0, false, ch * 4, &s, "")) return 1;
         }
         sc = s;
+      }
+      if (cfg.use_se) {
+        // squeeze-excitation (nn.py:506-517): the gate from the pooled t2 (conv3 + BN folded into fc1: upload_se_gate), conv3
+        // without residual / ReLU, then out = max(y * gate + shortcut, 0) in one pass (resnet_se.hip)
+        ODT_CHECK(t2.C == ch && t2.H == Ho && t2.W == Wo, "SE block: conv2's output is not dense in " + pre);
+        ODT_CHECK(sc.C == ch * 4 && sc.H == Ho && sc.W == Wo && sc.h == Ho && sc.w == Wo,
+                  "SE block: shortcut / conv3 geometry mismatch in " + pre);
+        Op og; og.kind = OP_RSE_GATE;
+        ResSeParams& gp = og.rse;
+        gp.t2 = t2.d; gp.B = B; gp.HW = Ho * Wo; gp.ch = ch; gp.r = ch / 4; gp.cout = ch * 4; gp.gate_ld = ch * 4;
+        if (upload_se_gate(m, pre, ch, &gp.w1, &gp.b1, &gp.w2t, &gp.b2)) return 1;
+        gp.part = m->alloc_f((size_t)B * channel_mean_splits(gp.HW, ch, B) * ch, false);
+        gp.mean = m->alloc_f((size_t)B * ch, false);
+        gp.rvec = m->alloc_f((size_t)B * gp.r, false);
+        gp.gate = m->alloc_f((size_t)B * gp.gate_ld, true);
+        ODT_CHECK(gp.part && gp.mean && gp.rvec && gp.gate, "device allocation failed (SE gate of " + pre + ")");
+        m->ops.push_back(og);
+        { Tensor gt{}; gt.d = gp.gate; gt.B = 1; gt.H = gt.h = 1; gt.W = gt.w = B; gt.C = gt.c = gp.gate_ld; m->taps[pre + "/se_gate"] = gt; }
+        if (upload_conv(m, pre + "/conv3", 1, 1, ch, ch * 4, true, &wt, &bias)) return 1;
+        if (add_conv(m, pre + "/conv3", t2, ch, wt, bias, 1, 1, ch * 4, 1, 1, 0, 0, Ho, Wo, 0, 0, nullptr, 0,
+                     false, ch * 4, &y, "")) return 1;
+        Tensor o{};
+        if (make_tensor(m, tap, B, Ho, Wo, ch * 4, &o)) return 1;
+        Op oa; oa.kind = OP_RSE_APPLY; oa.out = o;
+        ResSeApplyParams& ap = oa.rsa;
+        ap.y = y.d; ap.sc = sc.d; ap.gate = gp.gate; ap.out = o.d; ap.amax = nullptr;
+        ap.B = B; ap.HW = Ho * Wo; ap.C = ch * 4; ap.ldc = ch * 4; ap.gate_ld = gp.gate_ld;
+        m->ops.push_back(oa);
+        ++m->se_blocks;
+        x = o;
+        cin = ch * 4;
+        continue;
       }
       if (upload_conv(m, pre + "/conv3", 1, 1, ch, ch * 4, true, &wt, &bias)) return 1;
       if (add_conv(m, pre + "/conv3", t2, ch, wt, bias, 1, 1, ch * 4, 1, 1, 0, 0, Ho, Wo, 0, 0, &sc, 1,

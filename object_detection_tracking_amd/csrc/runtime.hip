@@ -119,6 +119,12 @@ static int run_ops(odt_model* m, const void* src, int dtype, hipStream_t st, siz
       case OP_ROI_EFF:
         if (launch_roi_align(m->roi_eff, st)) return 1;
         break;
+      case OP_RSE_GATE:           // SE-ResNet: pool of conv2's output -> gate (conv3 + BN folded into fc1)
+        if (launch_resnet_se_gate(op.rse, st)) return 1;
+        break;
+      case OP_RSE_APPLY:          // ... and out = max(conv3 * gate + shortcut, 0)
+        if (launch_resnet_se_apply(op.rsa, st)) return 1;
+        break;
       case OP_MASK_SELECT:
         if (launch_mask_select(m->mask_sel, st)) return 1;
         break;
@@ -697,6 +703,15 @@ int odt_describe(odt_handle h, char* buf, int cap) {
     fam[c.p.wt_split != nullptr ? conv_variant_row(c.p.variant).family : CF_F32] += 1;
     if (c.p.wt_split != nullptr && c.p.splitk > 1) ++nsk;
   }
+  // SE-ResNet: the blocks' conv1 layers that read their input -- the previous block's apply output -- on the fp16x2 kernels
+  // (they can only where the apply kernel recorded that tensor's range)
+  int se_conv1_h2 = 0;
+  if (h->se_blocks > 0)
+    for (const ConvOp& c : h->convs) {
+      const size_t n = c.name.size();
+      if (n > 6 && c.name.compare(n - 6, 6, "/conv1") == 0 && c.p.wt_split != nullptr && conv_variant_row(c.p.variant).family == CF_H2)
+        ++se_conv1_h2;
+    }
   size_t dev_bytes = 0;
   for (const auto& b : h->bufs) dev_bytes += b->bytes;
   dev_bytes += h->frames_src.bytes;
@@ -716,13 +731,14 @@ int odt_describe(odt_handle h, char* buf, int cap) {
                 "\"one_stage_bk32\": %d, \"h2_8wave_lds_dma\": %d, \"of_split3_with_split_k\": %d}, \"policy\": {\"family\": %d, \"min_tiles\": %ld, "
                 "\"min_tiles3\": %ld, \"min_k\": %d}, \"env_overrides_applied\": %d, \"env_overrides\": [%s], "
                 "\"memory\": {\"device_bytes\": %zu, \"activation_arena_bytes\": [%zu, %zu], \"arena_tensors\": %zu, "
-                "\"arena_tensor_bytes_unshared\": %zu, \"dedicated_tensor_bytes\": %zu, \"keep_taps\": %d}, \"convs_cut_into_batch_ranges\": %d}",
+                "\"arena_tensor_bytes_unshared\": %zu, \"dedicated_tensor_bytes\": %zu, \"keep_taps\": %d}, \"convs_cut_into_batch_ranges\": %d, "
+                "\"use_se\": %d, \"se_blocks\": %d, \"se_blocks_conv1_on_fp16x2\": %d}",
                 h->policy.arith != 0 && fam[2] > 0 ? "f32 through fp16x2 / bf16x3 split products"
                     : (h->policy.arith != 0 && fam[1] + fam[3] > 0 ? "f32 through bf16x3 split products" : "exact f32 MFMA"),
                 (int)h->convs.size() - nfused, nfused, fam[0], fam[1] + fam[3], fam[2], h->convs_h2f, h->stem_fused, h->mb_fused, fam[3], fam[1], fam[2], nsk, h->policy.family,
                 h->policy.min_tiles, h->policy.min_tiles3, h->policy.min_k, (int)active.size(), envs.c_str(),
                 dev_bytes, h->arena_bytes[0], h->arena_bytes[1], h->vt.size(), h->virtual_tensor_bytes,
-                h->dedicated_tensor_bytes, h->cfg.keep_taps, h->chunked_convs);
+                h->dedicated_tensor_bytes, h->cfg.keep_taps, h->chunked_convs, h->cfg.use_se != 0 ? 1 : 0, h->se_blocks, se_conv1_h2);
   ODT_CHECK((int)std::strlen(tmp) < cap, "odt_describe: buffer too small");
   std::strncpy(buf, tmp, cap - 1); buf[cap - 1] = 0;
   return 0;

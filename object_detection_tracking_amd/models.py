@@ -131,6 +131,7 @@ class _Engine(object):
     # default plans the activations into an arena (a stage's memory is reused once its consumers have run)
     c.keep_taps = int(bool(getattr(config, "keep_taps", False)))
     c.tail_overlap = -1 if getattr(config, "tail_overlap", True) in (False, -1) else 0      # (False: everything on the compute stream)
+    c.use_se = int(bool(getattr(config, "use_se", False)))      # model version 6: squeeze-excitation in every bottleneck
     B, P, Cn = batch, self.per_im, self.channels
     self._boxes = np.zeros((B, P, 4), np.float32)
     self._probs = np.zeros((B, P), np.float32)
@@ -348,6 +349,19 @@ class _Engine(object):
     return out
 
 
+def _missing_se_variables(weights, num_blocks):
+  """Names of the squeeze-excitation variables (groupG/blockI/fc1/{W,b}, fc2/{W,b}; W as [in, out]) that ``weights`` lacks
+  or holds in another shape."""
+  bad = []
+  for g, (ch, cnt) in enumerate(zip((64, 128, 256, 512), num_blocks)):
+    for i in range(int(cnt)):
+      pre = "group%d/block%d/" % (g, i)
+      for name, shape in (("fc1/W", (4 * ch, ch // 4)), ("fc1/b", (ch // 4,)), ("fc2/W", (ch // 4, 4 * ch)), ("fc2/b", (4 * ch,))):
+        if pre + name not in weights or tuple(np.shape(weights[pre + name])) != shape:
+          bad.append(pre + name)
+  return bad
+
+
 class _DetectorBase(object):
   graph = ODT_GRAPH_SINGLE
 
@@ -373,13 +387,20 @@ class _DetectorBase(object):
         raise ValueError("weights: pass a {name: array} dict or set config.model_path to a "
                          "Tensorpack-style .npz (reference obj_detect_tracking.py:417-435), a "
                          "TF checkpoint directory / prefix, or a frozen .pb (--is_load_from_pb)")
-    unsupported = [f for f in ("use_se", "use_gn", "use_resnext", "use_deformable", "add_relation_nn",
+    unsupported = [f for f in ("use_gn", "use_resnext", "use_deformable", "add_relation_nn",
                                "use_conv_frcnn_head", "use_att_frcnn_head",
                                "use_small_object_head", "use_cascade_rcnn")
                    if getattr(self.config, f, False)]
     if unsupported:
       raise NotImplementedError("graph variants not built on this path (SURVEY.md 8, out of scope): "
                                 + ", ".join(unsupported))
+    if getattr(self.config, "use_se", False):
+      # version 6 (nn.py:506-517): every bottleneck carries fc1 / fc2.  Checked here, not at the first frame: a plan cannot be
+      # built without them, and a model that cannot run should not construct
+      missing = _missing_se_variables(weights, self.config.resnet_num_block)
+      if missing:
+        raise NotImplementedError("an SE graph cannot be built from weights without squeeze-excitation variables: missing "
+                                  + ", ".join(missing[:4]) + (" ... (%d in all)" % len(missing) if len(missing) > 4 else ""))
     # --use_partial_classes (reference models.py:807-829): class-subset head
     self.head_num_class = int(self.config.num_class)
     if getattr(self.config, "use_frcnn_class_agnostic", False):
@@ -605,7 +626,8 @@ def config_from_weights(weights, add_mask=False, is_multi=False, **overrides):
   graph is in the file; here the file is a weight container, so what the graph would say is read off the shapes):
   bottlenecks per stage, classes, FPN / head widths, class-agnostic box head.  Everything that is a graph constant
   rather than a tensor (rpn_test_post_nms_topk, thresholds, frame size) keeps the reference's defaults unless
-  overridden."""
+  overridden.  ``group0/block0/fc1/W`` present means a squeeze-excitation backbone (use_se); unless overridden,
+  use_dilations=False follows from it: the only published SE model (version 6) is undilated."""
   from .config import make_config
   blocks = [0, 0, 0, 0]
   for k in weights:
@@ -618,6 +640,8 @@ def config_from_weights(weights, add_mask=False, is_multi=False, **overrides):
   kw = dict(resnet_num_block=blocks, num_class=num_class, add_mask=bool(add_mask),
             use_frcnn_class_agnostic=(nbox == 4 or nbox == 8) and num_class > 2,
             im_batch_size=2 if is_multi else 1)
+  if "group0/block0/fc1/W" in weights:
+    kw.update(use_se=True, use_dilations=False)
   kw.update(overrides)
   cfg = make_config(**kw)
   cfg.fpn_num_channel = int(np.asarray(weights["fpn/lateral_1x1_c2/W"]).shape[-1])

@@ -403,3 +403,61 @@ def mask_rle(masks, boxes, frame_hw, scale=1.0, want_counts=False, device_ptrs=N
   del keep
   rles = res.rles()
   return (rles, res.count_lists()) if want_counts else rles
+
+
+def se_fold(w3, b3, fc1_w, fc1_b):
+  """conv3 + BN folded into the SE gate's first layer (mean_HW commutes with a 1x1 conv and an affine BN): w3 [ch, 4 ch] with
+  the BN scale folded in, b3 [4 ch] the BN shift -> (w1 [r][ch], b1 [r]) in float64, rounded to float32 once -- what the plan
+  does at build time (csrc/plan_common.hip upload_se_gate)."""
+  w3 = np.asarray(w3, np.float64); f1 = np.asarray(fc1_w, np.float64)
+  w1 = (w3 @ f1).T
+  b1 = np.asarray(b3, np.float64) @ f1 + np.asarray(fc1_b, np.float64)
+  return f32(w1), f32(b1)
+
+
+def rse_gate(t2, w1, b1, w2t, b2, lib=None, device=0):
+  """SE-ResNet gate as the plan runs it: t2 [B,H,W,ch] -> spatial mean -> relu(. w1 + b1) (w1 [r][ch]) -> sigmoid(. w2t + b2)
+  (w2t [r][cout]).  Returns (mean [B,ch], gate [B,cout])."""
+  lib = _L(lib)
+  t2 = f32(t2); w1 = f32(w1); b1 = f32(b1); w2t = f32(w2t); b2 = f32(b2)
+  B, ch = t2.shape[0], t2.shape[-1]
+  HW = t2.size // (B * ch)
+  r, cout = w2t.shape
+  assert w1.shape == (r, ch) and b1.shape == (r,) and b2.shape == (cout,)
+  mean = np.empty((B, ch), np.float32); gate = np.empty((B, cout), np.float32)
+  lib.check(lib.dll.odt_op_rse_gate(device, fptr(t2), B, HW, ch, r, cout, fptr(w1), fptr(b1), fptr(w2t), fptr(b2), fptr(mean),
+                                    fptr(gate)))
+  return mean, gate
+
+
+def rse_apply(y, gate, shortcut, C=None, in_place=False, out_init=None, lib=None, device=0):
+  """out = max(y * gate[b, c] + shortcut, 0) over the first C channels of [B,...,ldc] tensors (gate [B,ldc]); channels [C, ldc)
+  of the result keep what out_init holds (default zeros).  Returns (out, recorded |max| of out)."""
+  lib = _L(lib)
+  y = f32(y); s = f32(shortcut); g = f32(gate)
+  B, ldc = y.shape[0], y.shape[-1]
+  HW = y.size // (B * ldc)
+  C = ldc if C is None else int(C)
+  assert s.shape == y.shape and g.shape == (B, ldc)
+  out = np.zeros(y.shape, np.float32) if out_init is None else f32(out_init).copy()
+  amax = np.zeros(1, np.float32)
+  lib.check(lib.dll.odt_op_rse_apply(device, fptr(y), fptr(g), fptr(s), B, HW, C, ldc, int(bool(in_place)), fptr(out), fptr(amax)))
+  return out, float(amax[0])
+
+
+def se_tail(t2, w3, b3, fc1, fc2, shortcut, lib=None, device=0):
+  """The tail of an SE bottleneck (reference nn.py:502-521) as the plan runs it: pool of t2 [B,H,W,ch] -> gate (conv3 + BN
+  folded into fc1 = (W [4 ch, ch / 4], b), fc2 = (W [ch / 4, 4 ch], b)) -> conv3 (w3 [ch, 4 ch] with BN folded, + b3) ->
+  max(conv3 * gate + shortcut, 0).  Returns (out [B,H,W,4 ch], gate [B,4 ch], recorded |max| of out)."""
+  lib = _L(lib)
+  t2 = f32(t2); w3 = f32(w3); b3 = f32(b3); s = f32(shortcut)
+  B, H, W, ch = t2.shape
+  C3 = w3.shape[1]
+  assert C3 == 4 * ch and s.shape == (B, H, W, C3)
+  w1, b1 = se_fold(w3, b3, fc1[0], fc1[1])
+  w2t = f32(fc2[0]); b2 = f32(fc2[1])
+  assert w2t.shape == (ch // 4, C3)
+  out = np.empty((B, H, W, C3), np.float32); gate = np.empty((B, C3), np.float32); amax = np.zeros(1, np.float32)
+  lib.check(lib.dll.odt_op_se_tail(device, fptr(t2), B, H, W, ch, fptr(w3), fptr(b3), fptr(w1), fptr(b1), fptr(w2t), fptr(b2),
+                                   fptr(s), fptr(out), fptr(gate), fptr(amax)))
+  return out, gate, float(amax[0])

@@ -116,6 +116,22 @@ def synthetic_weights(config, seed=0):
   nb = 1 if getattr(config, "use_frcnn_class_agnostic", False) else nc   # models.py:1164
   w["fastrcnn/outputs/box/W"] = normal((dim, nb * 4), 0.01)
   w["fastrcnn/outputs/box/b"] = normal((nb * 4,), 0.002)
+  if getattr(config, "use_se", False):
+    # squeeze-excitation (version 6, nn.py:506-517) from a generator of its own: everything above is bit-identical to the
+    # non-SE weights of the same seed.  Wide fc2 so that the gates spread over (0, 1) and a missing gate shows
+    se_rng = np.random.default_rng([seed, 6])
+
+    def se_normal(shape, std):
+      return se_rng.standard_normal(shape, dtype=np.float32) * np.float32(std)
+
+    for g, (feat, cnt) in enumerate(zip((64, 128, 256, 512), config.resnet_num_block)):
+      for i in range(cnt):
+        pre = "group%d/block%d" % (g, i)
+        C, r = 4 * feat, feat // 4
+        w[pre + "/fc1/W"] = se_normal((C, r), np.sqrt(2.0 / C))
+        w[pre + "/fc1/b"] = se_normal((r,), 0.02)
+        w[pre + "/fc2/W"] = se_normal((r, C), np.sqrt(2.0 / r))
+        w[pre + "/fc2/b"] = se_normal((C,), 0.5)
   return w
 
 
