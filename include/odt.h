@@ -104,6 +104,11 @@ typedef struct odt_config {
   int32_t use_se;           /* model version 6: squeeze-excitation in every ResNet bottleneck (nn.py:506-517; variables
                              * groupG/blockI/fc1/{W,b}, fc2/{W,b}, W as [in, out]): l * sigmoid(fc2(relu(fc1(mean_HW(l))))) between
                              * conv3 + BN and the residual add */
+  int32_t block_kind;       /* the backbone's block function (nn.py:864-868): 0 resnet_bottleneck | 1 resnet_basicblock (--resnet18 /
+                             * --resnet34: conv1 3x3 stride s 'SAME', conv2 3x3, identity or 1x1 convshortcut; stages of 64 / 128 / 256 /
+                             * 512 channels; dilations ignored) | 2 resnext_32x4d_bottleneck (--use_resnext: conv1 1x1 to 2 ch, conv2
+                             * 3x3 in 32 groups with stride and dilation 'SAME' (W [3,3,2ch/32,2ch]), conv3 1x1 to 4 ch).  Neither
+                             * 1 nor 2 combines with use_se */
 } odt_config;
 
 /* conv_arith: all modes keep f32 tensors and f32 accumulation.  ODT_ARITH_F32: every product on the exact-f32 MFMA
@@ -469,6 +474,12 @@ int odt_op_rse_apply(int device, const float* y, const float* gate, const float*
 int odt_op_se_tail(int device, const float* t2, int B, int H, int W, int ch, const float* w3, const float* b3, const float* w1,
                    const float* b1, const float* w2t, const float* b2, const float* shortcut, float* out, float* gate,
                    float* amax);
+/* 3x3 convolution in 32 groups (csrc/conv_group.hip; ResNeXt-32x4d conv2, nn.py:536-539) as the plan runs it: x [B,H,W,C], C in
+ * {128, 256, 512, 1024}; w grouped HWIO [3,3,C/32,C] (output channel o reads input channels (o / (C/32)) (C/32) ...); bias [C];
+ * stride, dil in {1, 2}; pad_t / pad_l zeros before, taps past H x W read zero; relu 0 / 1 -> out [B,Ho,Wo,C], amax [1]: the
+ * |max| the kernel recorded for out.  Plain f32, fixed summation order. */
+int odt_op_group_conv(int device, const float* x, int B, int H, int W, int C, const float* w, const float* bias, int stride,
+                      int dil, int pad_t, int pad_l, int Ho, int Wo, int relu, float* out, float* amax);
 /* BiFPN node input fusion (launch_bifpn_fuse): n = 1..3 inputs ins[k] [B,in_hw[k][0],in_hw[k][1],ldc], mode[k] 0 same
  * size, 1 nearest resize, 2 3x3 / s2 'SAME' max pool with pads[k] = (top, left); wsm != NULL: 'fastattn' with the raw
  * WSM scalars [n], else a plain sum; act 0 / 2 (swish).  out [B,h,w,ldc]. */

@@ -46,7 +46,8 @@ def make_config(**overrides):
   c.add_mask = False
   c.use_gn = False
   c.use_se = False
-  c.use_resnext = False
+  c.use_resnext = False           # ResNeXt-32x4d blocks (--use_resnext); takes precedence over use_basic_block (nn.py:864-868)
+  c.resnet152 = c.resnet50 = c.resnet34 = c.resnet18 = False
   c.use_deformable = False
   c.use_frcnn_class_agnostic = False
   c.use_conv_frcnn_head = False
@@ -104,8 +105,20 @@ def finalize_config(c):
   c.fpn_num_channel = 256
   c.fpn_frcnn_fc_head_dim = 1024
   d.setdefault("mrcnn_head_dim", 256)          # obj_detect_tracking.py:324
+  # backbone depth flags (obj_detect_tracking.py:188-191, 348-359): a set flag decides the block counts and the block
+  # function, as there; without one a given resnet_num_block / use_basic_block stands (R101 bottlenecks by default)
   d.setdefault("resnet_num_block", [3, 4, 23, 3])
-  c.use_basic_block = False
+  d.setdefault("use_basic_block", False)  # for resnet-34 and resnet-18
+  if getattr(c, "resnet152", False):
+    c.resnet_num_block = [3, 8, 36, 3]
+  if getattr(c, "resnet50", False):
+    c.resnet_num_block = [3, 4, 6, 3]
+  if getattr(c, "resnet34", False):
+    c.resnet_num_block = [3, 4, 6, 3]
+    c.use_basic_block = True
+  if getattr(c, "resnet18", False):
+    c.resnet_num_block = [2, 2, 2, 2]
+    c.use_basic_block = True
   c.anchor_sizes = (32, 64, 128, 256, 512)
   c.anchor_ratios = (0.5, 1, 2)
   c.num_anchors = len(c.anchor_sizes) * len(c.anchor_ratios)

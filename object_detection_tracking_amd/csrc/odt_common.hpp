@@ -395,6 +395,22 @@ struct ResSeApplyParams {
 };
 int launch_resnet_se_apply(const ResSeApplyParams& p, hipStream_t stream);
 
+// ------------------------------------------------------- 32-group 3x3 conv (conv_group.hip; ResNeXt-32x4d, reference nn.py:524-549)
+// out = act(bias + grouped 3x3 conv of in), dense NHWC f32, C = Cin = Cout in {128, 256, 512, 1024}, G = C / 32 channels per
+// group; taps outside H x W are zero; plain f32 in a fixed order in every arithmetic mode.
+struct GroupConvParams {
+  const float* in;     // [B,H,W,C]
+  const float* wt;     // group_conv_pack_weights image (BN scale folded)
+  const float* bias;   // [C]
+  float* out;          // [B,Ho,Wo,C]
+  unsigned* out_amax;  // range slot of out (|max| of what is stored) or nullptr
+  int B, H, W, C, Ho, Wo, stride, dil, pad_t, pad_l, relu;
+};
+size_t group_conv_weight_elems(int C);
+// hwio [3][3][C / 32][C] times scale[o] (nullptr: 1) in double, rounded once -> dst[group_conv_weight_elems(C)] (host memory)
+int group_conv_pack_weights(const float* hwio, const double* scale, int C, float* dst);
+int launch_group_conv(const GroupConvParams& p, hipStream_t stream);
+
 // ------------------------------------------------------- EfficientDet tail (effdet_post.hip)
 struct EffPostParams {
   const float* cls[5];     // per level [B, npix, ldc_cls]  (9 * ncls valid channels: anchor-major)

@@ -60,10 +60,11 @@ struct ConvOp {
 
 enum OpKind { OP_PRE, OP_CONV, OP_POOL, OP_SUB2, OP_PROPOSALS, OP_ROI_HEAD, OP_DETECT, OP_ROI_FINAL,
               OP_ROI_MASK, OP_MASK_SELECT, OP_PRE_RGB, OP_DW, OP_CMEAN, OP_CSCALE, OP_FUSE, OP_EFF_POST, OP_ROI_EFF, OP_SE_GATE,
-              OP_SE_GATE_MEAN, OP_WSCALE, OP_MB_EXPAND_DW, OP_RSE_GATE, OP_RSE_APPLY };
+              OP_SE_GATE_MEAN, OP_WSCALE, OP_MB_EXPAND_DW, OP_RSE_GATE, OP_RSE_APPLY, OP_GCONV };
 struct Op {
   OpKind kind;
   int conv = -1;        // index into convs
+  int gconv = -1;       // OP_GCONV: its index among the plan's grouped convs (profiling events)
   Tensor in, out;
   DwConvParams dw{};    // OP_DW
   MbExpandDwParams mb{};   // OP_MB_EXPAND_DW
@@ -71,6 +72,7 @@ struct Op {
   SeGateParams se{};    // OP_SE_GATE (aux2 = partial-sum scratch)
   ResSeParams rse{};    // OP_RSE_GATE: pool of conv2's output + the SE-ResNet gate
   ResSeApplyParams rsa{};   // OP_RSE_APPLY: gate * conv3 + shortcut, ReLU
+  GroupConvParams gc{};    // OP_GCONV: the ResNeXt block's 32-group 3x3 conv2 (conv_group.hip)
   float* aux = nullptr; // OP_CMEAN: means out [B,ldc]; OP_CSCALE / OP_WSCALE: gates in [B,ldc]
   const float* wt0 = nullptr;   // OP_WSCALE: the conv's unscaled weights [Cout][K] (conv = index of the conv whose weights are rebuilt)
   float* aux2 = nullptr;   // OP_CMEAN: partial-sum scratch
@@ -127,6 +129,7 @@ struct odt_model {
   Slot* d2h_slot = nullptr; int d2h_want = 0;
   ConvPolicy policy{};               // conv arithmetic / kernel-family policy of this handle (attach_split_weights)
   int se_blocks = 0;                 // SE-ResNet (odt_config.use_se): bottlenecks that run pool + gate + apply (resnet_se.hip)
+  int gconv_ops = 0;                 // ResNeXt (odt_config.block_kind == 2): launches of the 32-group 3x3 conv per forward (conv_group.hip)
   int mb_fused = 0;                  // EfficientNet: MBConv blocks whose expand + depthwise run as one kernel (effnet_mbconv.hip)
   // tail overlap: the selection / ROIAlign / box-head / NMS kernels of forward i (a few dozen workgroups each,
   // ~2 ms per 8-frame step) run on a side stream under the backbone of forward i+1.  The next forward's FPN stage
@@ -171,6 +174,9 @@ struct odt_model {
   hipEvent_t ev_total[2] = {nullptr, nullptr};
   double prof_conv_ms = 0, prof_conv_flops = 0, prof_total_ms = 0;
   std::vector<double> prof_layer_ms;
+  std::vector<hipEvent_t> ev_gconv;  // OP_GCONV i: events [2 i, 2 i + 1]
+  double prof_gconv_ms = 0;
+  int prof_forwards = 0;
   int prof_launches = 0;
 
   // ---- activation arena (odt_config.keep_taps == 0): stage tensors get VIRTUAL addresses while the plan is built
@@ -216,6 +222,7 @@ int upload_conv(odt_model* m, const std::string& scope, int kh, int kw, int cin,
 int upload_conv_cat(odt_model* m, const std::string& sa, int cin_a, const std::string& sb, int cin_b, int cout,
                     const float** wt_out, const float** bias_out);
 int upload_raw(odt_model* m, const std::vector<float>& v, const float** out);
+int upload_group_conv(odt_model* m, const std::string& scope, int C, const float** wt_out, const float** bias_out);
 int upload_se_gate(odt_model* m, const std::string& pre, int ch, const float** w1, const float** b1, const float** w2t,
                    const float** b2);
 int add_conv(odt_model* m, const std::string& name, const Tensor& in, int cin, const float* wt, const float* bias, int kh,
@@ -268,6 +275,7 @@ void visit_op_ptrs(odt_model* m, size_t oi, F&& f) {
     case OP_MB_EXPAND_DW: f(op.mb.x); f(op.mb.out); break;
     case OP_RSE_GATE: f(op.rse.t2); f(op.rse.part); f(op.rse.mean); f(op.rse.rvec); f(op.rse.gate); break;
     case OP_RSE_APPLY: f(op.rsa.y); f(op.rsa.sc); f(op.rsa.gate); f(op.rsa.out); break;
+    case OP_GCONV: f(op.gc.in); f(op.gc.out); break;
     case OP_FUSE: for (auto& p : op.fuse.in) f(p); f(op.fuse.out); break;
     case OP_EFF_POST: for (auto& p : m->eff_post.cls) f(p); for (auto& p : m->eff_post.box) f(p); break;
     case OP_CMEAN: case OP_CSCALE: case OP_SE_GATE: case OP_SE_GATE_MEAN: case OP_WSCALE: case OP_POOL: case OP_SUB2: break;

@@ -864,6 +864,30 @@ int odt_op_se_tail(int device, const float* t2, int B, int H, int W, int ch, con
   return get_dev(out, dout, M * C3);
 }
 
+int odt_op_group_conv(int device, const float* x, int B, int H, int W, int C, const float* w, const float* bias, int stride,
+                      int dil, int pad_t, int pad_l, int Ho, int Wo, int relu, float* out, float* amax) {
+  ODT_CHECK(x && w && bias && out && amax, "odt_op_group_conv: null argument");
+  ODT_CHECK(B >= 1 && H >= 1 && W >= 1 && Ho >= 1 && Wo >= 1, "odt_op_group_conv: bad sizes");
+  ODT_CHECK(C == 128 || C == 256 || C == 512 || C == 1024, "odt_op_group_conv: C must be 128, 256, 512 or 1024");
+  if (set_dev(device)) return 1;
+  std::vector<float> img(group_conv_weight_elems(C));
+  if (group_conv_pack_weights(w, nullptr, C, img.data())) return 1;
+  GBufs g;
+  GroupConvParams p; std::memset(&p, 0, sizeof(p));
+  const size_t nin = (size_t)B * H * W * C, nout = (size_t)B * Ho * Wo * C;
+  float *dx, *dw, *db, *dout;
+  unsigned* slot;
+  if (g.alloc("x", nin, &dx, -1, x) || g.alloc("w", img.size(), &dw, -1, img.data()) || g.alloc("bias", (size_t)C, &db, -1, bias) ||
+      g.alloc("out", nout, &dout) || g.alloc("range slot", (size_t)kAmaxWays, &slot, 0)) return 1;
+  p.in = dx; p.wt = dw; p.bias = db; p.out = dout; p.out_amax = slot;
+  p.B = B; p.H = H; p.W = W; p.C = C; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.dil = dil; p.pad_t = pad_t; p.pad_l = pad_l;
+  p.relu = relu ? 1 : 0;
+  if (launch_group_conv(p, nullptr)) return 1;
+  if (g.check("odt_op_group_conv")) return 1;
+  if (rse_read_amax(slot, amax)) return 1;
+  return get_dev(out, dout, nout);
+}
+
 int odt_op_effdet_post(int device, int B, int ncls, const int32_t* npix, int ldc_cls, int ldc_box,
                        const float* const* cls, const float* const* box, const float* anchors, int k, int max_out,
                        float score_thresh, float iou_thresh, float image_scale, int32_t* cand_idx, float* cand_boxes,

@@ -115,6 +115,29 @@ int upload_conv_cat(odt_model* m, const std::string& sa, int cin_a, const std::s
   return 0;
 }
 
+// The ResNeXt block's grouped conv2 (W [3,3,C/32,C], nn.py:536-539) with its BN folded in double, as upload_conv does, and
+// re-packed for the kernel (group_conv_pack_weights).
+int upload_group_conv(odt_model* m, const std::string& scope, int C, const float** wt_out, const float** bias_out) {
+  const HostTensor* W = find_w(m, scope + "/W");
+  const HostTensor* g = find_w(m, scope + "/bn/gamma");
+  const HostTensor* b = find_w(m, scope + "/bn/beta");
+  const HostTensor* mu = find_w(m, scope + "/bn/mean/EMA");
+  const HostTensor* var = find_w(m, scope + "/bn/variance/EMA");
+  ODT_CHECK(W != nullptr, "missing weight " + scope + "/W");
+  ODT_CHECK(g && b && mu && var, "missing BN variables for " + scope);
+  ODT_CHECK(W->data.size() == group_conv_weight_elems(C), "bad shape for " + scope + "/W (a 32-group 3x3 conv: [3,3,C/32,C])");
+  ODT_CHECK(g->data.size() == (size_t)C && b->data.size() == (size_t)C && mu->data.size() == (size_t)C &&
+            var->data.size() == (size_t)C, "bad BN shapes for " + scope);
+  std::vector<double> scale(C);
+  std::vector<float> bias(C), img(group_conv_weight_elems(C));
+  for (int o = 0; o < C; ++o) {
+    scale[o] = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5);
+    bias[o] = (float)((double)b->data[o] - (double)mu->data[o] * scale[o]);
+  }
+  if (group_conv_pack_weights(W->data.data(), scale.data(), C, img.data())) return 1;
+  return upload_raw(m, img, wt_out) || upload_raw(m, bias, bias_out);
+}
+
 // The SE gate of bottleneck `pre` (reference nn.py:506-517) with conv3 + BN folded into fc1.  conv3 is 1x1 and BN affine, so
 // mean_HW(BN(conv3(t2))) = BN(conv3(mean_HW(t2))):
 //   w1[j][i] = sum_o conv3/W[i][o] * bnscale[o] * fc1/W[o][j]      b1[j] = sum_o bnshift[o] * fc1/W[o][j] + fc1/b[j]
@@ -294,6 +317,18 @@ int attach_split_weights(odt_model* m) {
       if (m->range_slot_name[slot].empty()) m->range_slot_name[slot] = "SE block output";
       continue;
     }
+    if (op.kind == OP_GCONV) {
+      // the grouped conv's output: the kernel records its range as a conv epilogue would, so that conv3 keeps the fp16x2 kernels
+      slot_of.erase(op.gc.out);
+      if (pol.family != 2) continue;
+      const int g = tail ? 1 : 0;
+      ODT_CHECK(m->amax_used[g] < odt_model::kAmaxSlots, "too many conv outputs for the range slots");
+      const int slot = (tail ? odt_model::kAmaxSlots : 0) + m->amax_used[g]++;
+      slot_of[op.gc.out] = slot;
+      m->ops[oi].gc.out_amax = m->amax_dev + (size_t)slot * kAmaxWays;
+      m->range_slot_name[slot] = "grouped conv2 output";
+      continue;
+    }
     if (op.kind == OP_POOL || op.kind == OP_SUB2) {
       auto it = slot_of.find(op.in.d);
       if (it != slot_of.end()) slot_of[op.out.d] = it->second; else slot_of.erase(op.out.d);
@@ -437,6 +472,8 @@ int fuse_bottleneck_tails(odt_model* m) {
   if (m->policy.arith == 0 || m->policy.family != 2) return 0;
   // SE blocks stay as they are: the fused tail never materialises conv2's output, which the gate pools, and its epilogue has no gate
   if (m->cfg.use_se) return 0;
+  // basic and ResNeXt blocks have no dense 3x3 + 1x1 pair
+  if (m->cfg.block_kind != 0) return 0;
   std::map<const float*, const void*> made;
   for (size_t oi = 0; oi + 1 < m->ops.size(); ++oi) {
     Op& oa = m->ops[oi]; Op& ob = m->ops[oi + 1];

@@ -61,12 +61,96 @@ int build_plan(odt_model* m) {
   Tensor cfeat[4];
   const int feats[4] = {64, 128, 256, 512};
   int cin = 64;
+  ODT_CHECK(cfg.block_kind >= 0 && cfg.block_kind <= 2, "odt_config.block_kind must be 0 (bottleneck), 1 (basic) or 2 (ResNeXt-32x4d)");
+  ODT_CHECK(cfg.block_kind == 0 || !cfg.use_se, "squeeze-excitation is built for the plain bottleneck only (block_kind 0)");
+  // conv2d's default padding (nn.py:337-381), TensorFlow's 'SAME': out = ceil(in / s), the smaller half of the padding in
+  // front.  The rest lies behind the input, where the kernels read zeros anyway
+  auto same_pad = [](int in, int s, int keff, int* out, int* before) {
+    *out = (in + s - 1) / s;
+    *before = std::max((*out - 1) * s + keff - in, 0) / 2;
+  };
+  // resnet_shortcut (nn.py:551-566) as a conv of its own: 1x1, stride 2 VALID on x[:, :, :-1, :-1], BN, no ReLU
+  auto shortcut_conv = [&](const std::string& pre, const Tensor& x, int cin, int cout, int stride, int Ho, int Wo, Tensor* s) -> int {
+    if (upload_conv(m, pre + "/convshortcut", 1, 1, cin, cout, true, &wt, &bias)) return 1;
+    Tensor xc = x;
+    if (stride == 2) { xc.h = x.h - 1; xc.w = x.w - 1; }
+    ODT_CHECK((xc.h - 1) / stride + 1 == Ho && (xc.w - 1) / stride + 1 == Wo, "shortcut / block geometry mismatch in " + pre);
+    return add_conv(m, pre + "/convshortcut", xc, cin, wt, bias, 1, 1, cout, stride, 1, 0, 0, Ho, Wo, 0, 0, nullptr, 0, false,
+                    cout, s, "");
+  };
   for (int g = 0; g < 4; ++g) {
     const int cnt = cfg.num_blocks[g], ch = feats[g];
     for (int i = 0; i < cnt; ++i) {
       const std::string pre = "group" + std::to_string(g) + "/block" + std::to_string(i);
       const int stride = (i == 0 && g > 0) ? 2 : 1;
       const int dil = (g == 3 && cfg.use_dilations && i >= cnt - 3) ? 2 : 1;
+      if (cfg.block_kind == 1) {
+        // resnet_basicblock (nn.py:439-456; --resnet18 / --resnet34): conv1 3x3 stride s 'SAME' + BN + ReLU, conv2 3x3 + BN,
+        // + shortcut (the input itself where cin == ch, which includes group0/block0), ReLU.  `dilations` is ignored there
+        const std::string btap = (i == cnt - 1) ? "c" + std::to_string(g + 2) : (i == 0 ? pre : "");
+        int Ho, Wo, pt, pl;
+        same_pad(x.h, stride, 3, &Ho, &pt); same_pad(x.w, stride, 3, &Wo, &pl);
+        Tensor t1{}, sc = x, y{};
+        if (upload_conv(m, pre + "/conv1", 3, 3, cin, ch, true, &wt, &bias)) return 1;
+        if (add_conv(m, pre + "/conv1", x, cin, wt, bias, 3, 3, ch, stride, 1, pt, pl, Ho, Wo, 0, 0, nullptr, 0, true, ch, &t1, ""))
+          return 1;
+        if (cin != ch) {
+          Tensor s{};
+          if (shortcut_conv(pre, x, cin, ch, stride, Ho, Wo, &s)) return 1;
+          sc = s;
+        }
+        ODT_CHECK(sc.H == Ho && sc.W == Wo && sc.h == Ho && sc.w == Wo, "basic block: shortcut / conv2 geometry mismatch in " + pre);
+        if (upload_conv(m, pre + "/conv2", 3, 3, ch, ch, true, &wt, &bias)) return 1;
+        if (add_conv(m, pre + "/conv2", t1, ch, wt, bias, 3, 3, ch, 1, 1, 1, 1, Ho, Wo, 0, 0, &sc, 1, true, ch, &y, btap)) return 1;
+        x = y;
+        cin = ch;
+        continue;
+      }
+      if (cfg.block_kind == 2) {
+        // resnext_32x4d_bottleneck (nn.py:524-549; --use_resnext): conv1 1x1 to 2 ch, conv2 3x3 in 32 groups with the block's
+        // stride AND dilation under 'SAME' (conv_group.hip), conv3 1x1 to 4 ch + the bottleneck's shortcut, ReLU
+        const std::string btap = (i == cnt - 1) ? "c" + std::to_string(g + 2) : (i == 0 ? pre : "");
+        const int C2 = ch * 2;
+        int Ho, Wo, pt, pl;
+        same_pad(x.h, stride, 2 * dil + 1, &Ho, &pt); same_pad(x.w, stride, 2 * dil + 1, &Wo, &pl);
+        Tensor t1{}, t2{}, sc = x, y{};
+        if (upload_conv(m, pre + "/conv1", 1, 1, cin, C2, true, &wt, &bias)) return 1;
+        if (add_conv(m, pre + "/conv1", x, cin, wt, bias, 1, 1, C2, 1, 1, 0, 0, x.h, x.w, 0, 0, nullptr, 0, true, C2, &t1, ""))
+          return 1;
+        ODT_CHECK(t1.C == C2 && t1.H == t1.h && t1.W == t1.w, "ResNeXt block: conv1's output is not dense in " + pre);
+        if (make_tensor(m, "", B, Ho, Wo, C2, &t2)) return 1;
+        {
+          Op og; og.kind = OP_GCONV;
+          GroupConvParams& gp = og.gc;
+          if (upload_group_conv(m, pre + "/conv2", C2, &gp.wt, &gp.bias)) return 1;
+          gp.in = t1.d; gp.out = t2.d; gp.out_amax = nullptr;
+          gp.B = B; gp.H = t1.h; gp.W = t1.w; gp.C = C2; gp.Ho = Ho; gp.Wo = Wo;
+          gp.stride = stride; gp.dil = dil; gp.pad_t = pt; gp.pad_l = pl; gp.relu = 1;
+          og.gconv = m->gconv_ops++;
+          m->ops.push_back(og);
+        }
+        if (cin != ch * 4 && !m->knobs.off(K_FUSE_SHORTCUT)) {
+          // stage entry: conv3(t2) + convshortcut(x[::stride]) as one K-concatenated GEMM, as in the plain bottleneck below
+          ODT_CHECK((x.h - stride) / stride + 1 == Ho && (x.w - stride) / stride + 1 == Wo, "shortcut / conv2 geometry mismatch in " + pre);
+          if (upload_conv_cat(m, pre + "/conv3", C2, pre + "/convshortcut", cin, ch * 4, &wt, &bias)) return 1;
+          if (add_conv(m, pre + "/conv3+shortcut", t2, C2, wt, bias, 1, 1, ch * 4, 1, 1, 0, 0, Ho, Wo, 0, 0, nullptr, 0, true,
+                       ch * 4, &y, btap)) return 1;
+          ConvParams& cp = m->convs.back().p;
+          cp.in2 = x.d; cp.Cin2 = cin; cp.in2_ldc = x.C; cp.in2_Ha = x.H; cp.in2_Wa = x.W; cp.in2_stride = stride;
+        } else {
+          if (cin != ch * 4) {
+            Tensor s{};
+            if (shortcut_conv(pre, x, cin, ch * 4, stride, Ho, Wo, &s)) return 1;
+            sc = s;
+          }
+          if (upload_conv(m, pre + "/conv3", 1, 1, C2, ch * 4, true, &wt, &bias)) return 1;
+          if (add_conv(m, pre + "/conv3", t2, C2, wt, bias, 1, 1, ch * 4, 1, 1, 0, 0, Ho, Wo, 0, 0, &sc, 1, true, ch * 4, &y, btap))
+            return 1;
+        }
+        x = y;
+        cin = ch * 4;
+        continue;
+      }
       Tensor t1{}, t2{}, sc = x, y{};
       if (upload_conv(m, pre + "/conv1", 1, 1, cin, ch, true, &wt, &bias)) return 1;
       if (add_conv(m, pre + "/conv1", x, cin, wt, bias, 1, 1, ch, 1, 1, 0, 0, x.h, x.w, 0, 0, nullptr, 0,

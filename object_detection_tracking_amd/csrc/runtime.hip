@@ -125,6 +125,11 @@ static int run_ops(odt_model* m, const void* src, int dtype, hipStream_t st, siz
       case OP_RSE_APPLY:          // ... and out = max(conv3 * gate + shortcut, 0)
         if (launch_resnet_se_apply(op.rsa, st)) return 1;
         break;
+      case OP_GCONV:              // ResNeXt: the block's 32-group 3x3 conv2
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_gconv[2 * op.gconv], st));
+        if (launch_group_conv(op.gc, st)) return 1;
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_gconv[2 * op.gconv + 1], st));
+        break;
       case OP_MASK_SELECT:
         if (launch_mask_select(m->mask_sel, st)) return 1;
         break;
@@ -190,6 +195,12 @@ static int finish_profile(odt_model* m, hipStream_t st) {
     m->prof_layer_ms[i] += t;
     ++launched;
   }
+  for (int i = 0; i < m->gconv_ops; ++i) {
+    float t = 0;
+    ODT_HIP(hipEventElapsedTime(&t, m->ev_gconv[2 * i], m->ev_gconv[2 * i + 1]));
+    m->prof_gconv_ms += t;
+  }
+  ++m->prof_forwards;
   float tt = 0;
   ODT_HIP(hipEventElapsedTime(&tt, m->ev_total[0], m->ev_total[1]));
   m->prof_conv_ms += ms; m->prof_conv_flops += fl; m->prof_launches += launched;
@@ -234,6 +245,7 @@ int run_plan(odt_model* m, const void* frames, int dtype, int on_device, hipStre
   size_t ev_i = 0;
   if (m->profile) {
     while (m->ev.size() < 2 * m->convs.size()) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev.push_back(e); }
+    while (m->ev_gconv.size() < 2 * (size_t)m->gconv_ops) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_gconv.push_back(e); }
     for (int i = 0; i < 2; ++i) if (!m->ev_total[i]) ODT_HIP(hipEventCreate(&m->ev_total[i]));
     ODT_HIP(hipEventRecord(m->ev_total[0], st));
   }
@@ -320,6 +332,7 @@ int odt_destroy(odt_handle h) {
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
   for (auto e : h->ev) (void)hipEventDestroy(e);
+  for (auto e : h->ev_gconv) (void)hipEventDestroy(e);
   for (auto e : h->ev_total) if (e) (void)hipEventDestroy(e);
   for (auto& sl : h->slot) {
     if (sl.pin_in) (void)hipHostFree(sl.pin_in);
@@ -671,6 +684,7 @@ int odt_profile_enable(odt_handle h, int enable) {
   ODT_CHECK(h != nullptr, "null handle");
   h->profile = enable != 0;
   h->prof_conv_ms = h->prof_conv_flops = h->prof_total_ms = 0; h->prof_launches = 0;
+  h->prof_gconv_ms = 0; h->prof_forwards = 0;
   h->prof_layer_ms.assign(h->convs.size(), 0.0);
   return 0;
 }
@@ -732,13 +746,16 @@ int odt_describe(odt_handle h, char* buf, int cap) {
                 "\"min_tiles3\": %ld, \"min_k\": %d}, \"env_overrides_applied\": %d, \"env_overrides\": [%s], "
                 "\"memory\": {\"device_bytes\": %zu, \"activation_arena_bytes\": [%zu, %zu], \"arena_tensors\": %zu, "
                 "\"arena_tensor_bytes_unshared\": %zu, \"dedicated_tensor_bytes\": %zu, \"keep_taps\": %d}, \"convs_cut_into_batch_ranges\": %d, "
-                "\"use_se\": %d, \"se_blocks\": %d, \"se_blocks_conv1_on_fp16x2\": %d}",
+                "\"use_se\": %d, \"se_blocks\": %d, \"se_blocks_conv1_on_fp16x2\": %d, \"block_kind\": \"%s\", \"group_conv_launches\": %d, "
+                "\"group_conv_profiled_ms\": %.6f, \"profiled_forwards\": %d}",
                 h->policy.arith != 0 && fam[2] > 0 ? "f32 through fp16x2 / bf16x3 split products"
                     : (h->policy.arith != 0 && fam[1] + fam[3] > 0 ? "f32 through bf16x3 split products" : "exact f32 MFMA"),
                 (int)h->convs.size() - nfused, nfused, fam[0], fam[1] + fam[3], fam[2], h->convs_h2f, h->stem_fused, h->mb_fused, fam[3], fam[1], fam[2], nsk, h->policy.family,
                 h->policy.min_tiles, h->policy.min_tiles3, h->policy.min_k, (int)active.size(), envs.c_str(),
                 dev_bytes, h->arena_bytes[0], h->arena_bytes[1], h->vt.size(), h->virtual_tensor_bytes,
-                h->dedicated_tensor_bytes, h->cfg.keep_taps, h->chunked_convs, h->cfg.use_se != 0 ? 1 : 0, h->se_blocks, se_conv1_h2);
+                h->dedicated_tensor_bytes, h->cfg.keep_taps, h->chunked_convs, h->cfg.use_se != 0 ? 1 : 0, h->se_blocks, se_conv1_h2,
+                h->cfg.block_kind == 1 ? "basic" : (h->cfg.block_kind == 2 ? "resnext32x4d" : "bottleneck"), h->gconv_ops,
+                h->prof_gconv_ms, h->prof_forwards);
   ODT_CHECK((int)std::strlen(tmp) < cap, "odt_describe: buffer too small");
   std::strncpy(buf, tmp, cap - 1); buf[cap - 1] = 0;
   return 0;

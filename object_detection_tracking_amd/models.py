@@ -33,7 +33,7 @@ from .nn import get_new_hw
 from .range_guard import RangeGuard
 from .frozen_pb import load_frozen_pb
 from .tf_checkpoint import load_checkpoint
-from .weights import expand_class_agnostic_box, load_npz, select_partial_classes
+from .weights import backbone_block_kind, expand_class_agnostic_box, load_npz, select_partial_classes
 
 
 class TensorHandle(object):
@@ -132,6 +132,7 @@ class _Engine(object):
     c.keep_taps = int(bool(getattr(config, "keep_taps", False)))
     c.tail_overlap = -1 if getattr(config, "tail_overlap", True) in (False, -1) else 0      # (False: everything on the compute stream)
     c.use_se = int(bool(getattr(config, "use_se", False)))      # model version 6: squeeze-excitation in every bottleneck
+    c.block_kind = backbone_block_kind(config)                  # include/odt.h: 0 bottleneck | 1 basic | 2 ResNeXt-32x4d
     B, P, Cn = batch, self.per_im, self.channels
     self._boxes = np.zeros((B, P, 4), np.float32)
     self._probs = np.zeros((B, P), np.float32)
@@ -387,13 +388,19 @@ class _DetectorBase(object):
         raise ValueError("weights: pass a {name: array} dict or set config.model_path to a "
                          "Tensorpack-style .npz (reference obj_detect_tracking.py:417-435), a "
                          "TF checkpoint directory / prefix, or a frozen .pb (--is_load_from_pb)")
-    unsupported = [f for f in ("use_gn", "use_resnext", "use_deformable", "add_relation_nn",
+    unsupported = [f for f in ("use_gn", "use_deformable", "add_relation_nn",
                                "use_conv_frcnn_head", "use_att_frcnn_head",
                                "use_small_object_head", "use_cascade_rcnn")
                    if getattr(self.config, f, False)]
     if unsupported:
       raise NotImplementedError("graph variants not built on this path (SURVEY.md 8, out of scope): "
                                 + ", ".join(unsupported))
+    for f in ("use_resnext", "use_basic_block"):
+      # the reference's basic and ResNeXt blocks take use_se and ignore it (nn.py:439-456, 524-549): a graph that silently
+      # differs from what a --version 6 checkpoint was trained as is worse than an error
+      if getattr(self.config, f, False) and getattr(self.config, "use_se", False):
+        raise NotImplementedError("graph variants not built on this path: %s together with use_se (the reference builds "
+                                  "these blocks without squeeze-excitation and says nothing)" % f)
     if getattr(self.config, "use_se", False):
       # version 6 (nn.py:506-517): every bottleneck carries fc1 / fc2.  Checked here, not at the first frame: a plan cannot be
       # built without them, and a model that cannot run should not construct
@@ -627,7 +634,8 @@ def config_from_weights(weights, add_mask=False, is_multi=False, **overrides):
   bottlenecks per stage, classes, FPN / head widths, class-agnostic box head.  Everything that is a graph constant
   rather than a tensor (rpn_test_post_nms_topk, thresholds, frame size) keeps the reference's defaults unless
   overridden.  ``group0/block0/fc1/W`` present means a squeeze-excitation backbone (use_se); unless overridden,
-  use_dilations=False follows from it: the only published SE model (version 6) is undilated."""
+  use_dilations=False follows from it: the only published SE model (version 6) is undilated.  No ``group0/block0/conv3/W``
+  means basic blocks (use_basic_block); a ``conv2/W`` of [3,3,C/32,C] means ResNeXt-32x4d (use_resnext)."""
   from .config import make_config
   blocks = [0, 0, 0, 0]
   for k in weights:
@@ -642,6 +650,12 @@ def config_from_weights(weights, add_mask=False, is_multi=False, **overrides):
             im_batch_size=2 if is_multi else 1)
   if "group0/block0/fc1/W" in weights:
     kw.update(use_se=True, use_dilations=False)
+  if "group0/block0/conv3/W" not in weights:
+    kw.update(use_basic_block=True)            # resnet_basicblock: two 3x3 convs, no conv3
+  else:
+    w2 = np.asarray(weights["group0/block0/conv2/W"]).shape
+    if w2[2] * 32 == w2[3]:
+      kw.update(use_resnext=True)              # conv2/W [3,3,C/32,C]: the 32-group conv of resnext_32x4d_bottleneck
   kw.update(overrides)
   cfg = make_config(**kw)
   cfg.fpn_num_channel = int(np.asarray(weights["fpn/lateral_1x1_c2/W"]).shape[-1])

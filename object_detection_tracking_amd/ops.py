@@ -445,6 +445,25 @@ def rse_apply(y, gate, shortcut, C=None, in_place=False, out_init=None, lib=None
   return out, float(amax[0])
 
 
+def group_conv(x, w, bias, stride=1, dil=1, pad=None, out_hw=None, relu=True, lib=None, device=0):
+  """3x3 convolution in 32 groups (ResNeXt-32x4d conv2; csrc/conv_group.hip): x [B,H,W,C], C in {128, 256, 512, 1024}, w
+  grouped HWIO [3,3,C/32,C], bias [C].  pad = (top, left) zeros in front and out_hw = (Ho, Wo) default to TensorFlow's
+  'SAME' (out = ceil(in / stride), the smaller half of the padding in front); taps past H x W read zero.  Returns
+  (out [B,Ho,Wo,C], recorded |max| of out)."""
+  lib = _L(lib)
+  x = f32(x); w = f32(w); bias = f32(bias)
+  B, H, W, C = x.shape
+  assert w.shape == (3, 3, C // 32, C) and bias.shape == (C,)
+  keff = 2 * dil + 1
+  same = [((n + stride - 1) // stride, max(((n + stride - 1) // stride - 1) * stride + keff - n, 0) // 2) for n in (H, W)]
+  Ho, Wo = out_hw if out_hw is not None else (same[0][0], same[1][0])
+  pt, pl = pad if pad is not None else (same[0][1], same[1][1])
+  out = np.empty((B, Ho, Wo, C), np.float32); amax = np.zeros(1, np.float32)
+  lib.check(lib.dll.odt_op_group_conv(device, fptr(x), B, H, W, C, fptr(w), fptr(bias), int(stride), int(dil), int(pt), int(pl),
+                                      int(Ho), int(Wo), int(bool(relu)), fptr(out), fptr(amax)))
+  return out, float(amax[0])
+
+
 def se_tail(t2, w3, b3, fc1, fc2, shortcut, lib=None, device=0):
   """The tail of an SE bottleneck (reference nn.py:502-521) as the plan runs it: pool of t2 [B,H,W,ch] -> gate (conv3 + BN
   folded into fc1 = (W [4 ch, ch / 4], b), fc2 = (W [ch / 4, 4 ch], b)) -> conv3 (w3 [ch, 4 ch] with BN folded, + b3) ->

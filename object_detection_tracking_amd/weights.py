@@ -27,23 +27,44 @@ def load_npz(path):
     return {_strip(k): np.asarray(z[k]) for k in z.files}
 
 
+def backbone_block_kind(config):
+  """0 bottleneck | 1 basic block (use_basic_block) | 2 ResNeXt-32x4d (use_resnext, which takes precedence: nn.py:864-868)."""
+  if getattr(config, "use_resnext", False):
+    return 2
+  return 1 if getattr(config, "use_basic_block", False) else 0
+
+
 def backbone_conv_specs(config):
   """Yield (scope, kh, cin, cout, has_bn, has_bias) for every conv on the path,
-  in execution order (reference nn.py:843-1014, models.py:979-1009)."""
+  in execution order (reference nn.py:843-1014, models.py:979-1009); cin is W's third dimension -- the channels per
+  group of a grouped conv."""
   blocks = config.resnet_num_block
+  kind = backbone_block_kind(config)
   yield ("conv0", 7, 3, 64, True, False)
   cin = 64
   for g, (feat, cnt) in enumerate(zip((64, 128, 256, 512), blocks)):
     for i in range(cnt):
       pre = "group%d/block%d" % (g, i)
-      yield (pre + "/conv1", 1, cin, feat, True, False)
-      yield (pre + "/conv2", 3, feat, feat, True, False)
-      yield (pre + "/conv3", 1, feat, feat * 4, True, False)
+      if kind == 1:       # resnet_basicblock (nn.py:439-456): a shortcut conv only where the width changes (not in group0)
+        yield (pre + "/conv1", 3, cin, feat, True, False)
+        yield (pre + "/conv2", 3, feat, feat, True, False)
+        if cin != feat:
+          yield (pre + "/convshortcut", 1, cin, feat, True, False)
+        cin = feat
+        continue
+      if kind == 2:       # resnext_32x4d_bottleneck (nn.py:524-549): conv2 in 32 groups, W [3,3,2 feat / 32,2 feat]
+        yield (pre + "/conv1", 1, cin, feat * 2, True, False)
+        yield (pre + "/conv2", 3, feat * 2 // 32, feat * 2, True, False)
+        yield (pre + "/conv3", 1, feat * 2, feat * 4, True, False)
+      else:
+        yield (pre + "/conv1", 1, cin, feat, True, False)
+        yield (pre + "/conv2", 3, feat, feat, True, False)
+        yield (pre + "/conv3", 1, feat, feat * 4, True, False)
       if i == 0:
         yield (pre + "/convshortcut", 1, cin, feat * 4, True, False)
       cin = feat * 4
   ch = config.fpn_num_channel
-  for i, c in enumerate((256, 512, 1024, 2048)):
+  for i, c in enumerate((64, 128, 256, 512) if kind == 1 else (256, 512, 1024, 2048)):
     yield ("fpn/lateral_1x1_c%d" % (i + 2), 1, c, ch, False, True)
   for i in range(4):
     yield ("fpn/posthoc_3x3_p%d" % (i + 2), 3, ch, ch, False, True)
@@ -58,13 +79,14 @@ def synthetic_weights(config, seed=0):
 
   Distributions follow SURVEY.md section 8(d): He-init convs, BN close to
   identity (so activations stay O(1) through 101 layers), the last BN gamma of
-  each bottleneck scaled by 0.12, RPN class bias +1 (so the top-K logits are
+  each block scaled by 0.12 (conv3/bn; conv2/bn of a basic block), RPN class bias +1 (so the top-K logits are
   positive and the multibatch zero-padding quirk does not starve the head), box-head ``class`` /
   ``box`` weights wide enough that several classes pass the 1e-4 score filter
   and boxes actually move.
   """
   rng = np.random.default_rng(seed)
   w = {}
+  basic = backbone_block_kind(config) == 1
 
   def normal(shape, std):
     return (rng.standard_normal(shape, dtype=np.float32) * np.float32(std))
@@ -86,7 +108,7 @@ def synthetic_weights(config, seed=0):
       w[scope + "/b"] = b
     if has_bn:
       gamma = rng.uniform(0.9, 1.1, cout).astype(np.float32)
-      if scope.endswith("/conv3"):
+      if scope.endswith("/conv3") or (basic and scope.endswith("/conv2")):      # the block's last BN
         gamma *= np.float32(0.12)
       w[scope + "/bn/gamma"] = gamma
       w[scope + "/bn/beta"] = normal((cout,), 0.02)

@@ -1,0 +1,128 @@
+#!/usr/bin/env python
+"""The detector step of the backbones the plan can build, on one MI355X: ResNet-101 (the default), ResNeXt-101 32x4d
+(--use_resnext, [3,4,23,3]), ResNet-18 and ResNet-34 (--resnet18 / --resnet34).
+
+python tools/bench_backbones.py [--batch 8] [--height 1080] [--width 1920] [--topk 300] [--steps 10] [--warmup 2]
+  One child process per backbone (a fresh runtime each; nothing of one handle is resident under the next).  Multi graph,
+  --rotate resident uint8 batches taken in turn, device-synchronised timing after a warm-up (as bench.py).  Synthetic
+  weights of seed 0.  For ResNeXt a second, profiled pass times every launch of the 32-group 3x3 conv (csrc/conv_group.hip)
+  and prints the mean next to two floors computed here from the shapes: the bytes of its two tensors over the project's
+  measured copy rate, and its f32 products over the measured rate of the exact-f32 MFMA.
+python tools/bench_backbones.py --only resnext101 --steps 3
+  Just that handle in this process: the program to put behind `rocprofv3 --kernel-trace --stats --` for per-kernel times.
+One JSON line per backbone, and one with all of them at the end."""
+import argparse, json, os, subprocess, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+COPY_RATE = 6.29e12      # bytes/s, the project's measured device copy rate
+F32_MFMA_RATE = 155e12   # FLOP/s, v_mfma_f32_16x16x4_f32 back to back on every SIMD
+BACKBONES = {"r101": {}, "resnext101": dict(use_resnext=True), "resnet34": dict(resnet34=True), "resnet18": dict(resnet18=True)}
+
+
+def group_conv_shapes(cfg, B, H, W):
+  """[(C, H, W, Ho, Wo, stride, dil)] of the plan's grouped convs, by the plan's rules: the frame padded to a multiple of
+  32, a quarter of it after conv0 + pool0, 'SAME' at stride 2 on the stage entries."""
+  h, w = -(-H // 32) * 32 // 4, -(-W // 32) * 32 // 4
+  out = []
+  for g, (ch, cnt) in enumerate(zip((64, 128, 256, 512), cfg.resnet_num_block)):
+    for i in range(cnt):
+      stride = 2 if (i == 0 and g > 0) else 1
+      dil = 2 if (g == 3 and cfg.use_dilations and i >= cnt - 3) else 1
+      ho, wo = -(-h // stride), -(-w // stride)
+      out.append((2 * ch, h, w, ho, wo, stride, dil))
+      h, w = ho, wo
+  return out
+
+
+def child(a, name):
+  import torch
+  from object_detection_tracking_amd import models
+  from object_detection_tracking_amd._lib import ODT_DTYPE_U8
+  from object_detection_tracking_amd.config import make_config
+  from object_detection_tracking_amd.weights import synthetic_frames, synthetic_weights
+  B, H, W = a.batch, a.height, a.width
+  cfg = make_config(rpn_test_post_nms_topk=a.topk, im_batch_size=B, max_size=max(H, W), short_edge_size=min(H, W), **BACKBONES[name])
+  weights = synthetic_weights(cfg, seed=0)
+  frames = [synthetic_frames(B, H, W, seed=1234 + 77 * r) for r in range(max(1, a.rotate))]
+  dev = [torch.from_numpy(f).cuda(a.device) for f in frames]
+  torch.cuda.synchronize()
+  m = models.get_model(cfg, a.device, weights=weights, is_multi=True)
+  e = m.engine(B, H, W)
+  e.forward_device_async(dev[0].data_ptr(), ODT_DTYPE_U8); e.synchronize()      # bring-up: the range guard's comparison
+  k = [0]
+
+  def run(n):
+    for _ in range(n):
+      e.forward_device_async(dev[k[0] % len(dev)].data_ptr(), ODT_DTYPE_U8)
+      k[0] += 1
+    e.synchronize(); torch.cuda.synchronize()
+
+  run(a.warmup)
+  ms = []
+  for _ in range(a.rounds):
+    t0 = time.perf_counter()
+    run(a.steps)
+    ms.append((time.perf_counter() - t0) / a.steps * 1e3)
+  d = e.describe()
+  res = {"backbone": name, "blocks": list(cfg.resnet_num_block), "block_kind": d["block_kind"], "batch": B, "height": H, "width": W,
+         "topk": a.topk, "step_ms_per_round": ms, "step_ms": float(np.median(ms)), "fps": B * 1e3 / float(np.median(ms)),
+         "detections_last": int(e.read_outputs(False, False)[3].sum()), "conv_launches": d["conv_launches"],
+         "fp16x2_split_launches": d["fp16x2_split_launches"], "bottleneck_tails_fused": d["bottleneck_tails_fused"],
+         "group_conv_launches": d["group_conv_launches"], "range_guard": d.get("conv_split_family_auto", {}).get("chosen")}
+  if d["group_conv_launches"] > 0:
+    e.profile(True)
+    run(a.steps)
+    dp = e.describe()
+    e.profile(False)
+    shapes = group_conv_shapes(cfg, B, H, W)
+    assert len(shapes) == d["group_conv_launches"], (len(shapes), d["group_conv_launches"])
+    by = sum(4.0 * B * C * (h * w + ho * wo) for C, h, w, ho, wo, _, _ in shapes)
+    fl = sum(2.0 * B * ho * wo * C * 9 * (C // 32) for C, h, w, ho, wo, _, _ in shapes)
+    per_fwd = dp["group_conv_profiled_ms"] / max(1, dp["profiled_forwards"])
+    res["group_conv"] = {"ms_per_step": per_fwd, "ms_per_launch": per_fwd / len(shapes), "bytes_per_step": by, "flop_per_step": fl,
+                         "floor_ms_bytes_over_copy_rate": by / COPY_RATE * 1e3, "floor_ms_flop_over_f32_mfma_rate": fl / F32_MFMA_RATE * 1e3}
+  m.close()
+  print(json.dumps(res), flush=True)
+  return res
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument("--batch", type=int, default=8)
+  ap.add_argument("--height", type=int, default=1080)
+  ap.add_argument("--width", type=int, default=1920)
+  ap.add_argument("--topk", type=int, default=300)
+  ap.add_argument("--steps", type=int, default=10)
+  ap.add_argument("--warmup", type=int, default=2)
+  ap.add_argument("--rounds", type=int, default=3)
+  ap.add_argument("--rotate", type=int, default=4)
+  ap.add_argument("--only", default="", choices=[""] + sorted(BACKBONES))
+  ap.add_argument("--device", type=int, default=0)
+  a = ap.parse_args()
+  if a.only:
+    child(a, a.only)
+    return
+  out = {}
+  for name in BACKBONES:
+    cmd = [sys.executable, os.path.abspath(__file__), "--only", name] + \
+        [x for k in ("batch", "height", "width", "topk", "steps", "warmup", "rounds", "rotate", "device") for x in ("--" + k, str(getattr(a, k)))]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
+    if r.returncode != 0:
+      sys.exit("%s: child exited with %d" % (name, r.returncode))
+    res = json.loads(r.stdout.strip().splitlines()[-1])
+    out[name] = res
+    line = "%-11s %s %-12s %8.3f ms/step  %7.1f FPS  (%d conv launches, %d fused tails)" % (
+        name, res["blocks"], res["block_kind"], res["step_ms"], res["fps"], res["conv_launches"], res["bottleneck_tails_fused"])
+    print(line)
+    if "group_conv" in res:
+      g = res["group_conv"]
+      print("            grouped 3x3: %d launches, %.3f ms/step measured, %.4f ms/launch;  floors from shapes: %.2f GB -> %.3f ms at "
+            "%.2f TB/s, %.0f GFLOP -> %.3f ms at %.0f TF" % (res["group_conv_launches"], g["ms_per_step"], g["ms_per_launch"],
+            g["bytes_per_step"] / 1e9, g["floor_ms_bytes_over_copy_rate"], COPY_RATE / 1e12, g["flop_per_step"] / 1e9,
+            g["floor_ms_flop_over_f32_mfma_rate"], F32_MFMA_RATE / 1e12))
+  print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+  main()
