@@ -376,6 +376,12 @@ int odt_op_conv2d_cat(int device, const float* a, int B, int Ho, int Wo, int Ca,
 int odt_op_bottleneck_tail(int device, const float* in, int B, int H, int W, int C, const float* w2,
                            const float* b2, int dil, const float* w3, const float* b3, int C3,
                            const float* res, int relu3, int fuse, float* out);
+/* A whole identity bottleneck block (nn.py:503-521) on the fp16x2 kernels: out = relu(conv3(relu(conv2(relu(conv1(x))))) + x),
+ * conv1 1x1 4C -> C (w1 [4C,C]), conv2 3x3 stride 1 'SAME' C -> C (w2 [3,3,C,C] HWIO), conv3 1x1 C -> 4C (w3 [C,4C]), biases b1 [C],
+ * b2 [C], b3 [4C]; C = 64.  fuse = 1: one launch of conv_block_kernel (what the plan runs for the res2 identity blocks);
+ * fuse = 0: three launches, each conv's tensor written and read back.  x, out [B,H,W,4C]. */
+int odt_op_bottleneck_block(int device, const float* x, int B, int H, int W, int C, const float* w1, const float* b1,
+                            const float* w2, const float* b2, const float* w3, const float* b3, int fuse, float* out);
 /* The ResNet stem on an already padded frame tensor (nn.py:860-896 + 784-792): conv0 7x7 stride 2 VALID over frame_pad
  * [B,Hp,Wp,3] (+ bias, ReLU) -> 3x3 stride 2 max-pool over the top/left zero-padded map; fp16x2 arithmetic.  fuse = 1: the
  * one launch of conv_stem_kernel, 0: the two launches it replaces.  out: [B, Hq, Wq, 64], Hq = ((Hp - 7) / 2 + 1 + 1 - 3) / 2 + 1

@@ -347,8 +347,10 @@ __global__ void __launch_bounds__(256) h2_rowscale_kernel(const float* __restric
 
 // image: [n-tile][stage][piece 2][k-group 4][BN n][8 k] f16, stage order = (32-channel slice, tap) of the first source, then
 // the second source's slices; wt is [Cout][tap][Cin] (+ [Cin2] behind it); row n is multiplied by 2^t_n = 1 / chinv[n]
+// perm (conv_block_kernel's 3x3 conv): the k-groups of a stage carry the slice's channels in the order the MFMA C layout holds
+// them -- group kg, element e = channel 16 (kg / 2) + 4 (kg % 2) + (e % 4) + 8 (e / 4) of the slice (split_weights_h2f_kernel's order)
 __global__ void split_weights_h2_kernel(const float* __restrict__ wt, int Cout, int K, int SBN, int ntaps, int Cin,
-                                        unsigned short* __restrict__ img, const float* __restrict__ chinv) {
+                                        unsigned short* __restrict__ img, const float* __restrict__ chinv, int perm = 0) {
   const int nst = K >> 5, nst1 = ntaps * (Cin >> 5);
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;       // (n, stage, k-group)
   const long total = (long)cout_padded(Cout) * nst * 4;       // n over the padded Cout: zero rows behind the last channel
@@ -357,12 +359,13 @@ __global__ void split_weights_h2_kernel(const float* __restrict__ wt, int Cout, 
   int k0;
   if (st < nst1) { const int cs = st / ntaps, tap = st - cs * ntaps; k0 = tap * Cin + cs * 32; }
   else k0 = ntaps * Cin + (st - nst1) * 32;
-  k0 += kg * 8;
+  k0 += perm ? (kg >> 1) * 16 + (kg & 1) * 4 : kg * 8;
   const int tn = n / SBN, nn = n - tn * SBN;
   const float s = 1.0f / chinv[n];                            // (a power of two: exact)
   for (int e = 0; e < 8; e += 2) {
     unsigned piece[2];
-    const float w0 = n < Cout ? wt[(size_t)n * K + k0 + e] : 0.f, w1 = n < Cout ? wt[(size_t)n * K + k0 + e + 1] : 0.f;
+    const int ke = perm ? (e & 3) + 8 * (e >> 2) : e;         // (e even: element e + 1 is k + 1 either way)
+    const float w0 = n < Cout ? wt[(size_t)n * K + k0 + ke] : 0.f, w1 = n < Cout ? wt[(size_t)n * K + k0 + ke + 1] : 0.f;
     split2h(w0, w1, s, piece[0], piece[1]);
     for (int q = 0; q < 2; ++q) {
       const size_t at = ((((size_t)(tn * nst + st) * 2 + q) * 4 + kg) * SBN + nn) * 8 + e;
@@ -423,7 +426,19 @@ int conv_make_h2_weights(const ConvParams& p, void* img_dev, hipStream_t stream)
   hipLaunchKernelGGL(h2_rowscale_kernel, dim3((unsigned)cout_padded(p.Cout)), dim3(256), 0, stream, p.wt, p.Cout, K, chinv);
   const long total = (long)cout_padded(p.Cout) * (K >> 5) * 4;
   hipLaunchKernelGGL(split_weights_h2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p.wt, p.Cout, K,
-                     bn, p.kh * p.kw, p.Cin, (unsigned short*)img_dev, chinv);
+                     bn, p.kh * p.kw, p.Cin, (unsigned short*)img_dev, chinv, 0);
+  ODT_HIP(hipGetLastError());
+  return 0;
+}
+
+int conv_make_h2p_weights(const ConvParams& p, void* img_dev, hipStream_t stream) {
+  const int K = p.kh * p.kw * p.Cin;
+  ODT_CHECK(p.Cout == 64 && p.Cin == 64 && p.in2 == nullptr, "conv_make_h2p_weights: a 64 -> 64 conv required");
+  float* chinv = const_cast<float*>(conv_h2_chinv(img_dev, p.Cout, K));
+  hipLaunchKernelGGL(h2_rowscale_kernel, dim3(64u), dim3(256), 0, stream, p.wt, p.Cout, K, chinv);
+  const long total = (long)64 * (K >> 5) * 4;
+  hipLaunchKernelGGL(split_weights_h2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p.wt, p.Cout, K,
+                     64, p.kh * p.kw, p.Cin, (unsigned short*)img_dev, chinv, 1);
   ODT_HIP(hipGetLastError());
   return 0;
 }

@@ -622,7 +622,8 @@ double conv_flops(const ConvParams& p) {
   return 2.0 * (double)p.B * p.Ho * p.Wo * (double)p.Cout *
              (double)(p.kh * p.kw * p.Cin + (p.in2 != nullptr ? p.Cin2 : 0)) +
          (p.head_wt != nullptr ? 2.0 * (double)p.B * p.Ho * p.Wo * (double)p.Cout * 15.0 : 0.0) +   // fused 1x1 head (15 real columns)
-         (p.f_wt != nullptr ? 2.0 * (double)p.B * p.Ho * p.Wo * (double)p.Cout * (double)p.f_cout : 0.0);   // fused 1x1 conv
+         (p.f_wt != nullptr ? 2.0 * (double)p.B * p.Ho * p.Wo * (double)p.Cout * (double)p.f_cout : 0.0) +   // fused 1x1 conv
+         (p.b_wt2 != nullptr ? 2.0 * (double)p.B * p.Ho * p.Wo * (double)p.Cin * (double)p.b_cin : 0.0);     // 1x1 conv in front (OP_BLOCK)
 }
 
 int conv_check(const ConvParams& p) {

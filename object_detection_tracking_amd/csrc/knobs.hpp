@@ -15,7 +15,7 @@ namespace odt {
   X(CONV_H2_ROT) X(CONV_SPLIT3_FILLDIV) X(CONV_SPLIT3_BM) X(CONV_SPLIT3_SPLITK) X(CONV_SPLIT3_KWR) X(CONV_SPLIT3_KWR_N64)         \
   X(CONV_SPLIT3_FORCE_SPLITK) X(CONV_SPLIT_SRC2) X(CONV_SPLIT_RES2) X(SPLIT_REDUCE_BLOCKS) X(CONV_NT) X(AMAX_PER_WAVE) X(ROI_AMAX)            \
   X(CONV_CHUNK_BYTES) X(CONV_TILE) X(CONV_DEBUG) X(CONV_SMALLK) X(CONV_STAGES) X(CONV_FINE) X(CONV_TRACE)                         \
-  X(FUSE_SHORTCUT) X(FUSE_RPN_HEAD) X(FUSE_BOTTLENECK) X(FUSE_ROT) X(FUSE_STEM) X(STEM_GRID) X(TAIL_OVERLAP)                      \
+  X(FUSE_SHORTCUT) X(FUSE_RPN_HEAD) X(FUSE_BOTTLENECK) X(FUSE_BLOCK) X(FUSE_ROT) X(FUSE_STEM) X(STEM_GRID) X(TAIL_OVERLAP)                      \
   X(SIDE_STREAM_PRIORITY) X(COSINE_STREAM_PRIORITY) X(TRACKER_TIMING)                                                             \
   X(EFFDET_SPLIT) X(EFFDET_FUSE_MB) X(EFFDET_FUSE_MB_MIN) X(EFFDET_WSCALE) X(EFFDET_MERGE_LEVELS) X(DW_PX) X(DW_SUMCAP) X(DW_XCD)
 

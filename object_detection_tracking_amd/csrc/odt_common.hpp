@@ -135,11 +135,22 @@ struct ConvParams {
   int f_cout, f_out_ldc, f_res_ldc, f_relu;
   int host_unused1_[5];
   int reduce_blocks;   // block cap of the split-K combine pass (ODT_SPLIT_REDUCE_BLOCKS; conv_select)
+  // optional 1x1 conv IN FRONT of this 3x3 conv + fused tail (conv_block.hip: conv_block_kernel, the whole identity bottleneck
+  // out = relu(conv3(relu(conv2(relu(conv1(x))))) + x) in one launch; OP_BLOCK, fuse_bottleneck_blocks): conv1's output lives
+  // as an 18 x 18 pixel patch of fp16x2 pieces in LDS, `in` is never read.  Behind every field the other kernels know.
+  const float* b_in;         // x: [B,H,W,b_in_ldc], conv1's input (and, as f_res, the block's shortcut), or nullptr
+  const void* b_wt;          // conv1's weight image (conv_make_h2_weights, 64-wide n-tile)
+  const void* b_wt2;         // this conv's weight image with k in the patch's order (conv_make_h2p_weights)
+  const float* b_chinv;      // [64] conv1's inverse column powers of two
+  const float* b_bias;       // [64] conv1's bias
+  const unsigned* b_in_amax; // range slot of x
+  int b_cin, b_in_ldc;
 };
 // the device record does not move when a host-only slot changes its meaning (tests/test_kernel_resources.py: one awkward
 // field once pushed the kernels' copy of it into scratch)
-static_assert(sizeof(ConvParams) == 432 && offsetof(ConvParams, variant) == 208 && offsetof(ConvParams, splitk) == 224 &&
-              offsetof(ConvParams, nlvl) == 240 && offsetof(ConvParams, reduce_blocks) == 428, "ConvParams layout");
+static_assert(sizeof(ConvParams) == 488 && offsetof(ConvParams, variant) == 208 && offsetof(ConvParams, splitk) == 224 &&
+              offsetof(ConvParams, nlvl) == 240 && offsetof(ConvParams, reduce_blocks) == 428 && offsetof(ConvParams, b_in) == 432,
+              "ConvParams layout");
 // fills the derived fields (multiply-shift divisors)
 void conv_prepare(ConvParams& p);
 double conv_flops(const ConvParams& p);   // algorithmic 2*M*N*K
@@ -278,6 +289,11 @@ size_t conv_h2f_weight_bytes(int Cout, int K);
 const float* conv_h2f_chinv(const void* img, int Cout, int K);
 int conv_make_h2f_weights(const float* wt, int Cout, int K, void* img_dev, hipStream_t stream);
 bool conv_h2f_fusable(const ConvParams& a, const ConvParams& b);   // a: the KH x 3 producer, b: the 1x1 conv reading a.out
+// whole identity bottleneck in one kernel (conv_block.hip): a 64-wide 3x3 conv's image with k in the order conv1's accumulator
+// registers hold it (same size and row scales as conv_make_h2_weights'), the shape test, the launcher of an OP_BLOCK record
+int conv_make_h2p_weights(const ConvParams& p, void* img_dev, hipStream_t stream);
+bool conv_block_fits(const ConvParams& c1, const ConvParams& c2);    // c1: the 1x1 conv in front, c2: the 3x3 conv carrying the fused tail
+int launch_bottleneck_block(const ConvParams& p, const ConvParams* dev, hipStream_t stream);
 size_t conv_split_partial_bytes(const ConvParams& p);   // scratch a split-K conv needs (0: none)
 
 // ------------------------------------------------------------ elementwise (K1,K4)

@@ -60,10 +60,10 @@ struct ConvOp {
 
 enum OpKind { OP_PRE, OP_CONV, OP_POOL, OP_SUB2, OP_PROPOSALS, OP_ROI_HEAD, OP_DETECT, OP_ROI_FINAL,
               OP_ROI_MASK, OP_MASK_SELECT, OP_PRE_RGB, OP_DW, OP_CMEAN, OP_CSCALE, OP_FUSE, OP_EFF_POST, OP_ROI_EFF, OP_SE_GATE,
-              OP_SE_GATE_MEAN, OP_WSCALE, OP_MB_EXPAND_DW, OP_RSE_GATE, OP_RSE_APPLY, OP_GCONV };
+              OP_SE_GATE_MEAN, OP_WSCALE, OP_MB_EXPAND_DW, OP_RSE_GATE, OP_RSE_APPLY, OP_GCONV, OP_BLOCK };
 struct Op {
   OpKind kind;
-  int conv = -1;        // index into convs
+  int conv = -1;        // index into convs (OP_BLOCK: the block's conv2, whose record launches conv_block_kernel)
   int gconv = -1;       // OP_GCONV: its index among the plan's grouped convs (profiling events)
   Tensor in, out;
   DwConvParams dw{};    // OP_DW
@@ -94,7 +94,7 @@ struct odt_model {
   std::vector<std::unique_ptr<DevBuf>> bufs;
   std::map<std::string, Tensor> taps;
   std::vector<ConvOp> convs;
-  std::vector<char> conv_fused;      // convs[i] is evaluated inside another conv's kernel (no launch of its own): 1 RPN head, 2 bottleneck conv3
+  std::vector<char> conv_fused;      // convs[i] is evaluated inside another conv's kernel (no launch of its own): 1 RPN head, 2 bottleneck conv3, 3 bottleneck conv1 (OP_BLOCK)
   ConvParams* convs_dev = nullptr;   // device copies of conv_recs
   std::vector<ConvParams> conv_recs; // launch records: convs[i] runs as records [conv_rec0[i], + conv_nrec[i]) (batch ranges,
   std::vector<int> conv_rec0, conv_nrec;   // more than one only where a tensor would reach 2 GiB: upload_conv_records)
@@ -112,6 +112,7 @@ struct odt_model {
   int convs_h2 = 0;                  // convs on the fp16x2 kernels
   int stem_fused = 0;                // conv0 + pool0 run as one kernel (fuse_stem)
   int convs_h2f = 0;                 // ... of them with the following 1x1 conv folded into the kernel (fuse_bottleneck_tails)
+  int blocks_fused = 0;              // identity bottlenecks that run as one conv_block_kernel launch (fuse_bottleneck_blocks)
   unsigned* pre_amax = nullptr;      // range slot of the preprocessed frames (OP_PRE records it; conv0 reads it)
   std::vector<Op> ops;
   // geometry
@@ -233,6 +234,7 @@ ConvPolicy resolve_conv_policy(const odt_model* m);
 int attach_split_weights(odt_model* m);
 int fuse_rpn_heads(odt_model* m);
 int fuse_bottleneck_tails(odt_model* m);
+int fuse_bottleneck_blocks(odt_model* m);
 int fuse_stem(odt_model* m);
 void find_overlap_points(odt_model* m);
 int plan_arena(odt_model* m);
@@ -264,6 +266,8 @@ void visit_op_ptrs(odt_model* m, size_t oi, F&& f) {
   switch (op.kind) {
     case OP_PRE: case OP_PRE_RGB: f(m->image_pad.d); break;
     case OP_CONV: { ConvParams& c = m->convs[op.conv].p; f(c.in); f(c.res); f(c.out); f(c.in2); f(c.head_out); f(c.f_res); f(c.f_out); break; }
+    // (the block kernel reads x through b_in and as the shortcut f_res; `in` mirrors b_in: conv1's output does not exist)
+    case OP_BLOCK: { ConvParams& c = m->convs[op.conv].p; f(c.in); f(c.b_in); f(c.f_res); f(c.f_out); break; }
     case OP_PROPOSALS: for (auto& l : m->prop.lvl) f(l.rpn); f(m->prop.props); break;
     case OP_ROI_HEAD: roi(m->roi_head); break;
     case OP_ROI_FINAL: roi(m->roi_final); break;

@@ -369,6 +369,104 @@ int odt_op_bottleneck_tail(int device, const float* in, int B, int H, int W, int
   return dout.get(out, M * C3);
 }
 
+// x -> conv1 (1x1, 4C -> C, ReLU) -> conv2 (3x3 'SAME', ReLU) -> conv3 (1x1, C -> 4C, + x, ReLU) on the fp16x2 kernels, C = 64:
+// fuse = 1 as ONE conv_block_kernel launch (the plan's fuse_bottleneck_blocks), fuse = 0 as three launches with both
+// intermediate tensors and their recorded ranges.
+int odt_op_bottleneck_block(int device, const float* x, int B, int H, int W, int C, const float* w1_io, const float* b1,
+                            const float* w2_hwio, const float* b2, const float* w3_io, const float* b3, int fuse, float* out) {
+  ODT_CHECK(x && w1_io && b1 && w2_hwio && b2 && w3_io && b3 && out, "odt_op_bottleneck_block: null argument");
+  ODT_CHECK(C == 64 && B > 0 && H > 0 && W > 0, "odt_op_bottleneck_block: C = 64");
+  if (set_dev(device)) return 1;
+  const int C4 = 4 * C;
+  const size_t M = (size_t)B * H * W;
+  std::vector<float> w1((size_t)C * C4), w2((size_t)C * 9 * C), w3((size_t)C4 * C);
+  for (int i = 0; i < C4; ++i) for (int o = 0; o < C; ++o) w1[(size_t)o * C4 + i] = w1_io[(size_t)i * C + o];
+  for (int y = 0; y < 3; ++y) for (int xx = 0; xx < 3; ++xx) for (int i = 0; i < C; ++i) for (int o = 0; o < C; ++o)
+    w2[(((size_t)o * 3 + y) * 3 + xx) * C + i] = w2_hwio[(((size_t)y * 3 + xx) * C + i) * C + o];
+  for (int i = 0; i < C; ++i) for (int o = 0; o < C4; ++o) w3[(size_t)o * C + i] = w3_io[(size_t)i * C4 + o];
+  Tmp<float> dx, dw1, db1, dw2, db2, dw3, db3, dt1, dt2, dout, img1, img2, img2p, img3, imgf;
+  Tmp<unsigned> amax;
+  if (dx.alloc(M * C4) || dw1.alloc(w1.size()) || db1.alloc(C) || dw2.alloc(w2.size()) || db2.alloc(C) || dw3.alloc(w3.size()) ||
+      db3.alloc(C4) || dt1.alloc(M * C) || dt2.alloc(M * C) || dout.alloc(M * C4) || dout.zero() || amax.alloc(4 * kAmaxWays) || amax.zero()) return 1;
+  if (dx.put(x) || dw1.put(w1.data()) || db1.put(b1) || dw2.put(w2.data()) || db2.put(b2) || dw3.put(w3.data()) || db3.put(b3)) return 1;
+  if (launch_tensor_amax(dx.d, M * C4, amax.d, nullptr)) return 1;
+  ConvParams c1; std::memset(&c1, 0, sizeof(c1));
+  c1.in = dx.d; c1.wt = dw1.d; c1.bias = db1.d; c1.out = dt1.d;
+  c1.B = B; c1.H = H; c1.W = W; c1.Cin = C4; c1.in_ldc = C4; c1.in_Ha = H; c1.in_Wa = W; c1.Ho = H; c1.Wo = W; c1.Cout = C;
+  c1.kh = 1; c1.kw = 1; c1.stride = 1; c1.dil = 1; c1.out_H = H; c1.out_W = W; c1.out_ldc = C; c1.relu = 1;
+  conv_use_variant(c1, CV_H2_128x64);
+  c1.in_amax = amax.d; c1.out_amax = amax.d + kAmaxWays;
+  conv_prepare(c1);
+  if (img1.alloc((conv_split_weight_bytes(C, C4) + 3) / 4) || conv_make_split_weights(c1, img1.d, nullptr)) return 1;
+  c1.wt_split = img1.d; c1.h2_chinv = conv_h2_chinv(img1.d, C, C4);
+  ConvParams a; std::memset(&a, 0, sizeof(a));
+  a.in = dt1.d; a.wt = dw2.d; a.bias = db2.d; a.out = dt2.d;
+  a.B = B; a.H = H; a.W = W; a.Cin = C; a.in_ldc = C; a.in_Ha = H; a.in_Wa = W; a.Ho = H; a.Wo = W; a.Cout = C;
+  a.kh = 3; a.kw = 3; a.stride = 1; a.dil = 1; a.pad_t = 1; a.pad_l = 1;
+  a.out_H = H; a.out_W = W; a.out_ldc = C; a.relu = 1;
+  conv_use_variant(a, conv_variant_find(CF_H2, 256, C, CVF_KWR));
+  a.in_amax = amax.d + kAmaxWays; a.out_amax = amax.d + 2 * kAmaxWays; a.debug = 0x400;
+  conv_prepare(a);
+  if (img2.alloc((conv_split_weight_bytes(C, 9 * C) + 3) / 4) || conv_make_split_weights(a, img2.d, nullptr)) return 1;
+  a.wt_split = img2.d; a.h2_chinv = conv_h2_chinv(img2.d, C, 9 * C);
+  ConvParams b; std::memset(&b, 0, sizeof(b));
+  b.in = dt2.d; b.wt = dw3.d; b.bias = db3.d; b.out = dout.d; b.res = dx.d;
+  b.B = B; b.H = H; b.W = W; b.Cin = C; b.in_ldc = C; b.in_Ha = H; b.in_Wa = W; b.Ho = H; b.Wo = W; b.Cout = C4;
+  b.kh = 1; b.kw = 1; b.stride = 1; b.dil = 1;
+  b.out_H = H; b.out_W = W; b.out_ldc = C4; b.relu = 1;
+  b.res_mode = 1; b.res_H = H; b.res_W = W; b.res_ldc = C4;
+  conv_use_variant(b, CV_H2_256x256);
+  b.in_amax = amax.d + 2 * kAmaxWays; b.out_amax = amax.d + 3 * kAmaxWays; b.debug = 0x400;
+  conv_prepare(b);
+  if (img3.alloc((conv_split_weight_bytes(C4, C) + 3) / 4) || conv_make_split_weights(b, img3.d, nullptr)) return 1;
+  b.wt_split = img3.d; b.h2_chinv = conv_h2_chinv(img3.d, C4, C);
+  Tmp<ConvParams> rec;
+  if (rec.alloc(3)) return 1;
+  if (fuse) {
+    ODT_CHECK(conv_h2f_fusable(a, b), "odt_op_bottleneck_block: conv2 + conv3 are not fusable");
+    conv_use_variant(a, conv_variant_fused_tail(a.variant));
+    if (imgf.alloc((conv_h2f_weight_bytes(C4, C) + 3) / 4) || conv_make_h2f_weights(dw3.d, C4, C, imgf.d, nullptr)) return 1;
+    a.f_wt = imgf.d; a.f_chinv = conv_h2f_chinv(imgf.d, C4, C); a.f_bias = db3.d; a.f_res = dx.d; a.f_res_ldc = C4;
+    a.f_out = dout.d; a.f_out_ldc = C4; a.f_cout = C4; a.f_relu = 1; a.f_out_amax = amax.d + 3 * kAmaxWays;
+    a.out = nullptr; a.out_amax = nullptr;
+    ODT_CHECK(conv_block_fits(c1, a), "odt_op_bottleneck_block: this block does not fit conv_block_kernel");
+    if (img2p.alloc((conv_split_weight_bytes(C, 9 * C) + 3) / 4) || conv_make_h2p_weights(a, img2p.d, nullptr)) return 1;
+    a.b_in = dx.d; a.b_in_ldc = C4; a.b_cin = C4; a.b_wt = c1.wt_split; a.b_chinv = c1.h2_chinv; a.b_bias = c1.bias;
+    a.b_in_amax = c1.in_amax; a.b_wt2 = img2p.d;
+    a.in = dx.d; a.in_amax = c1.in_amax;      // (t1 does not exist)
+    // ODT_CONV_TRACE (tuning): per-phase wall-clock (100 MHz) averages over the workgroups
+    const bool trace = knobs_read().get(K_CONV_TRACE).set;
+    const size_t ntile = (size_t)B * ((H + 15) / 16) * ((W + 15) / 16);
+    Tmp<unsigned long long> tr;
+    if (trace) { if (tr.alloc(ntile * 16) || tr.zero()) return 1; a.trace = tr.d; }
+    ConvParams recs[3] = {a, c1, b};
+    if (conv_check(a) || rec.put(recs)) return 1;
+    if (launch_bottleneck_block(a, rec.d, nullptr)) return 1;
+    if (trace) {
+      ODT_HIP(hipDeviceSynchronize());
+      std::vector<unsigned long long> t(ntile * 16);
+      if (tr.get(t.data(), t.size())) return 1;
+      double ph[5] = {0, 0, 0, 0, 0};
+      unsigned long long t0 = ~0ull, t1 = 0;
+      for (size_t i = 0; i < ntile; ++i) {
+        const unsigned long long* q = &t[i * 16];
+        ph[0] += (double)(q[1] - q[0]); ph[1] += (double)(q[2] - q[1]); ph[2] += (double)(q[6] - q[2]); ph[3] += (double)(q[3] - q[6]); ph[4] += (double)(q[5] - q[3]);
+        if (q[0] < t0) t0 = q[0];
+        if (q[5] > t1) t1 = q[5];
+      }
+      printf("[block trace] tiles=%zu span=%.1f us | per tile avg us: conv1 loop %.2f  patch %.2f  conv2 %.2f  tail pieces %.2f  conv3 + stores %.2f\n",
+             ntile, (t1 - t0) / 100.0, ph[0] / ntile / 100, ph[1] / ntile / 100, ph[2] / ntile / 100, ph[3] / ntile / 100, ph[4] / ntile / 100);
+      fflush(stdout);
+    }
+  } else {
+    ConvParams recs[3] = {c1, a, b};
+    if (conv_check(c1) || conv_check(a) || conv_check(b) || rec.put(recs)) return 1;
+    if (launch_conv(c1, rec.d, nullptr) || launch_conv(a, rec.d + 1, nullptr) || launch_conv(b, rec.d + 2, nullptr)) return 1;
+  }
+  ODT_HIP(hipDeviceSynchronize());
+  return dout.get(out, M * C4);
+}
+
 int odt_op_stem(int device, const float* frame_pad, int B, int Hp, int Wp, const float* w_hwio, const float* bias, int fuse,
                 int grid, float* out) {
   ODT_CHECK(frame_pad && w_hwio && bias && out && B > 0 && Hp >= 11 && Wp >= 11, "odt_op_stem: null argument / frame too small");

@@ -513,6 +513,62 @@ int fuse_bottleneck_tails(odt_model* m) {
   return 0;
 }
 
+// ---- res2 identity bottlenecks as one kernel per block ------------------------------------------------------------------
+// block/conv1 (1x1, 256 -> 64, ReLU) -> block/conv2 (3x3, 64 -> 64, ReLU; already carrying the fused conv3 + shortcut + ReLU of
+// fuse_bottleneck_tails) where the shortcut is conv1's input and nothing else reads conv1's output: conv_block_kernel
+// (conv_block.hip) keeps conv1's output as an 18 x 18 pixel patch in LDS per 16 x 16 output pixels.  conv1's [M, 64] tensor is
+// neither written nor read back, x is read from HBM once instead of twice, conv1's launch disappears, and conv2's operand
+// gets its power of two per tile instead of per tensor.  conv2's record stays the launching record (its op becomes an
+// OP_BLOCK) and keeps its row of the kernel table; conv1's and conv3's ops are skipped.  A record that upload_conv_records
+// would cut into batch ranges (b = 24 @1080p) keeps the two launches.  A/B: profiles/block_fusion_res2_ab.txt.
+// ODT_FUSE_BLOCK=0 keeps the two launches, 2 fuses without the kernel's first-round stagger (A/B).  Called after fuse_bottleneck_tails, before fuse_stem and plan_arena.
+static int conv_batch_chunks(const ConvParams& p, double limit);
+int fuse_bottleneck_blocks(odt_model* m) {
+  if (m->knobs.off(K_FUSE_BLOCK)) return 0;
+  if (m->policy.arith == 0 || m->policy.family != 2 || m->cfg.use_se || m->cfg.block_kind != 0) return 0;
+  if (m->conv_fused.size() < m->convs.size()) m->conv_fused.resize(m->convs.size(), 0);
+  double limit = 2147483648.0;
+  if (m->knobs.get(K_CONV_CHUNK_BYTES).d > 0) limit = m->knobs.get(K_CONV_CHUNK_BYTES).d;
+  std::map<const float*, const void*> made;
+  for (size_t oi = 0; oi + 2 < m->ops.size(); ++oi) {
+    Op& o1 = m->ops[oi]; Op& o2 = m->ops[oi + 1]; Op& o3 = m->ops[oi + 2];
+    if (o1.kind != OP_CONV || o2.kind != OP_CONV || o3.kind != OP_CONV || o1.skip || o2.skip || !o3.skip) continue;
+    if (m->conv_fused[o3.conv] != 2) continue;
+    ConvOp& c1 = m->convs[o1.conv]; ConvOp& c2 = m->convs[o2.conv];
+    if (c2.p.variant != CV_H2KF_256x64 || c2.p.f_out != m->convs[o3.conv].p.out || !conv_block_fits(c1.p, c2.p)) continue;
+    // nothing else may read conv1's output
+    bool other = false;
+    for (size_t k = 0; k < m->ops.size() && !other; ++k) {
+      if (k == oi || k == oi + 1) continue;
+      visit_op_ptrs(m, k, [&](auto& ptr) { if ((const void*)ptr == (const void*)c1.p.out) other = true; });
+    }
+    for (const auto& kv : m->taps) if (kv.second.d == c1.p.out) other = true;
+    if (other) continue;
+    ConvParams q = c2.p;
+    q.in = c1.p.in; q.in_ldc = c1.p.in_ldc;
+    if (conv_batch_chunks(q, limit) != 1 || conv_batch_chunks(c1.p, limit) != 1) continue;
+    auto it = made.find(c2.p.wt);
+    if (it == made.end()) {
+      float* img = m->alloc_f((conv_split_weight_bytes(64, 9 * 64) + 3) / 4, false);
+      ODT_CHECK(img != nullptr, "device allocation failed (block weights of " + c2.name + ")");
+      if (conv_make_h2p_weights(c2.p, img, 0)) return 1;
+      it = made.emplace(c2.p.wt, img).first;
+    }
+    ConvParams& p = c2.p;
+    p.b_in = c1.p.in; p.b_in_ldc = c1.p.in_ldc; p.b_cin = c1.p.Cin; p.b_wt = c1.p.wt_split; p.b_chinv = c1.p.h2_chinv;
+    p.b_bias = c1.p.bias; p.b_in_amax = c1.p.in_amax; p.b_wt2 = it->second;
+    p.in = c1.p.in; p.in_amax = c1.p.in_amax;        // (conv1's output does not exist: the record names real memory only)
+    if ((c1.p.debug & 0x100) != 0) p.debug |= 0x100;
+    if (m->knobs.get(K_FUSE_BLOCK).c0 == '2') p.debug |= 0x200;      // A/B: no first-round stagger
+    o1.skip = true;
+    m->conv_fused[o1.conv] = 3;
+    o2.kind = OP_BLOCK;
+    ++m->blocks_fused;
+  }
+  ODT_HIP(hipDeviceSynchronize());
+  return 0;
+}
+
 // ---- conv0 + pool0 in one kernel ---------------------------------------------------------------------------------------
 // pool0 reads conv0's map and nothing else does (nn.py:860-896): where conv0 runs on the fp16x2 family the pair becomes one
 // launch of conv_stem_kernel (a 39 x 36 patch of the frame per 8 x 7 pooled pixels, split once into LDS; the [B,544,960,64] map
@@ -638,10 +694,10 @@ int plan_arena(odt_model* m) {
   // still hold its virtual address)
   for (size_t oi = 0; oi < m->ops.size(); ++oi) {
     const Op& op = m->ops[oi];
-    if (op.kind != OP_CONV || op.skip) continue;
+    if ((op.kind != OP_CONV && op.kind != OP_BLOCK) || op.skip) continue;
     const ConvParams& c = m->convs[op.conv].p;
     for (const void* q : {(const void*)c.in, (const void*)c.res, (const void*)c.out, (const void*)c.in2, (const void*)c.head_out,
-                          (const void*)c.f_res, (const void*)c.f_out})
+                          (const void*)c.f_res, (const void*)c.f_out, (const void*)c.b_in})
       ODT_CHECK(q == nullptr || !m->is_virtual(q), "activation arena: unmapped pointer left in " + m->convs[op.conv].name);
   }
   return 0;
@@ -672,7 +728,7 @@ int upload_conv_records(odt_model* m) {
   m->conv_recs.clear(); m->conv_rec0.clear(); m->conv_nrec.clear();
   std::vector<char> launched(m->convs.size(), 0);
   for (const Op& op : m->ops)
-    if (op.kind == OP_CONV && !op.skip) launched[op.conv] = 1;
+    if ((op.kind == OP_CONV || op.kind == OP_BLOCK) && !op.skip) launched[op.conv] = 1;
   for (size_t ci = 0; ci < m->convs.size(); ++ci) {
     const ConvOp& c = m->convs[ci];
     const ConvParams& p = c.p;

@@ -47,6 +47,14 @@ static int run_ops(odt_model* m, const void* src, int dtype, hipStream_t st, siz
         if (m->profile) ODT_HIP(hipEventRecord(m->ev[2 * op.conv + 1], st));
         break;
       }
+      case OP_BLOCK: {            // a whole identity bottleneck: conv2's record (never cut into batch ranges) launches conv_block_kernel
+        const ConvOp& c = m->convs[op.conv];
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev[2 * op.conv], st));
+        const int r = m->conv_rec0[op.conv];
+        if (m->conv_nrec[op.conv] != 1 || launch_bottleneck_block(m->conv_recs[r], m->convs_dev + r, st)) { g_err = c.name + ": " + g_err; return 1; }
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev[2 * op.conv + 1], st));
+        break;
+      }
       case OP_POOL:
         if (op.skip) break;
         if (launch_maxpool3x3s2(op.in.d, op.in.B, op.in.h, op.in.w, op.in.C, op.out.d, op.out.H, op.out.W, st)) return 1;
@@ -698,7 +706,9 @@ int odt_profile_layer(odt_handle h, int index, char* name, int name_cap, double*
   if (name && name_cap > 0) {    // layers on the bf16x3 split kernel are tagged (bench.py / profile_layers.py group by it)
     const bool fused = index < (int)h->conv_fused.size() && h->conv_fused[index];
     const ConvKernelRow& row = conv_variant_row(c.p.variant);
-    const std::string nm = c.name + (fused ? "[fused into the producer's epilogue]" : (c.p.head_wt != nullptr ? "+head" : ((row.flags & CVF_FTAIL) ? "+conv3" : ((row.flags & CVF_STEM) ? "+pool0" : "")))) +
+    const bool block = !fused && c.p.b_wt2 != nullptr;      // (the launching record of a fused block: .../conv2 -> .../conv1+conv2+conv3)
+    const size_t cut = c.name.rfind('/');
+    const std::string nm = (block && cut != std::string::npos ? c.name.substr(0, cut) + "/conv1+conv2" : c.name) + (fused ? (h->conv_fused[index] == 3 ? "[fused into the block kernel]" : "[fused into the producer's epilogue]") : (c.p.head_wt != nullptr ? "+head" : ((row.flags & CVF_FTAIL) ? "+conv3" : ((row.flags & CVF_STEM) ? "+pool0" : "")))) +
                            (!fused && c.p.wt_split != nullptr ? (row.family == CF_H2 ? "[fp16x2]" : "[bf16x3]") : "");
     std::strncpy(name, nm.c_str(), name_cap - 1); name[name_cap - 1] = 0;
   }
@@ -713,7 +723,9 @@ int odt_describe(odt_handle h, char* buf, int cap) {
   int fam[4] = {0, 0, 0, 0}, nsk = 0, nfused = 0;
   for (size_t i = 0; i < h->convs.size(); ++i) {
     const ConvOp& c = h->convs[i];
-    if (i < h->conv_fused.size() && h->conv_fused[i]) { ++nfused; continue; }
+    // (a block kernel's conv1 is folded in FRONT of its consumer, not into a producer's epilogue: "convs_fused_into_epilogues" and
+    // "conv_launches" = records outside epilogues keep their meaning; kernel launches = conv_launches - bottleneck_blocks_fused)
+    if (i < h->conv_fused.size() && h->conv_fused[i]) { if (h->conv_fused[i] != 3) ++nfused; continue; }
     fam[c.p.wt_split != nullptr ? conv_variant_row(c.p.variant).family : CF_F32] += 1;
     if (c.p.wt_split != nullptr && c.p.splitk > 1) ++nsk;
   }
@@ -741,7 +753,7 @@ int odt_describe(odt_handle h, char* buf, int cap) {
   char tmp[8192];
   std::snprintf(tmp, sizeof(tmp),
                 "{\"conv_arith\": \"%s\", \"conv_launches\": %d, \"convs_fused_into_epilogues\": %d, \"exact_f32_mfma_launches\": %d, "
-                "\"bf16x3_split_launches\": %d, \"fp16x2_split_launches\": %d, \"bottleneck_tails_fused\": %d, \"stem_fused\": %d, \"mbconv_expand_dw_fused\": %d, \"split_launches_by_family\": {\"split3_8wave_lds_dma\": %d, "
+                "\"bf16x3_split_launches\": %d, \"fp16x2_split_launches\": %d, \"bottleneck_tails_fused\": %d, \"bottleneck_blocks_fused\": %d, \"stem_fused\": %d, \"mbconv_expand_dw_fused\": %d, \"split_launches_by_family\": {\"split3_8wave_lds_dma\": %d, "
                 "\"one_stage_bk32\": %d, \"h2_8wave_lds_dma\": %d, \"of_split3_with_split_k\": %d}, \"policy\": {\"family\": %d, \"min_tiles\": %ld, "
                 "\"min_tiles3\": %ld, \"min_k\": %d}, \"env_overrides_applied\": %d, \"env_overrides\": [%s], "
                 "\"memory\": {\"device_bytes\": %zu, \"activation_arena_bytes\": [%zu, %zu], \"arena_tensors\": %zu, "
@@ -750,7 +762,7 @@ int odt_describe(odt_handle h, char* buf, int cap) {
                 "\"group_conv_profiled_ms\": %.6f, \"profiled_forwards\": %d}",
                 h->policy.arith != 0 && fam[2] > 0 ? "f32 through fp16x2 / bf16x3 split products"
                     : (h->policy.arith != 0 && fam[1] + fam[3] > 0 ? "f32 through bf16x3 split products" : "exact f32 MFMA"),
-                (int)h->convs.size() - nfused, nfused, fam[0], fam[1] + fam[3], fam[2], h->convs_h2f, h->stem_fused, h->mb_fused, fam[3], fam[1], fam[2], nsk, h->policy.family,
+                (int)h->convs.size() - nfused, nfused, fam[0], fam[1] + fam[3], fam[2], h->convs_h2f, h->blocks_fused, h->stem_fused, h->mb_fused, fam[3], fam[1], fam[2], nsk, h->policy.family,
                 h->policy.min_tiles, h->policy.min_tiles3, h->policy.min_k, (int)active.size(), envs.c_str(),
                 dev_bytes, h->arena_bytes[0], h->arena_bytes[1], h->vt.size(), h->virtual_tensor_bytes,
                 h->dedicated_tensor_bytes, h->cfg.keep_taps, h->chunked_convs, h->cfg.use_se != 0 ? 1 : 0, h->se_blocks, se_conv1_h2,

@@ -70,6 +70,21 @@ def bottleneck_tail(x, w2, b2, w3, b3, res=None, dil=1, relu3=True, fuse=True, l
   return out
 
 
+def bottleneck_block(x, w1, b1, w2, b2, w3, b3, fuse=True, lib=None, device=0):
+  """relu(conv3(relu(conv2(relu(conv1(x))))) + x): a stride-1 identity bottleneck (reference nn.py:503-521) on the fp16x2
+  kernels, x [B,H,W,4C], w1 [4C,C], w2 [3,3,C,C], w3 [C,4C], C = 64; fuse=True: conv_block_kernel (one launch), False: the
+  three convs as launches of their own."""
+  lib = _L(lib)
+  x = f32(x); w1 = f32(w1); b1 = f32(b1); w2 = f32(w2); b2 = f32(b2); w3 = f32(w3); b3 = f32(b3)
+  B, H, W, C4 = x.shape
+  Cc = w1.shape[1]
+  assert C4 == 4 * Cc and w1.shape[0] == C4 and w3.shape == (Cc, C4), (x.shape, w1.shape, w3.shape)
+  out = np.zeros((B, H, W, C4), np.float32)
+  lib.check(lib.dll.odt_op_bottleneck_block(device, fptr(x), B, H, W, Cc, fptr(w1), fptr(b1), fptr(w2), fptr(b2), fptr(w3),
+                                            fptr(b3), int(fuse), fptr(out)))
+  return out
+
+
 def stem(frame_pad, w_hwio, bias, fuse=True, grid=0, lib=None, device=0):
   """conv0 (7x7 stride 2 VALID + bias + ReLU) -> pool0 (3x3 stride 2 max over the top/left zero-padded map) on a padded frame
   tensor [B, Hp, Wp, 3] (reference nn.py:860-896, 784-792), fp16x2 arithmetic; fuse=True: conv_stem_kernel (one launch),
