@@ -399,6 +399,12 @@ int odt_op_stem(int device, const float* frame_pad, int B, int Hp, int Wp, const
 #define ODT_CONV_CHOICE_SHAPE 18
 #define ODT_CONV_CHOICE_OUT 11
 int odt_op_conv_choice(const int* shape, int conv_arith, int conv_split_family, int* out, char* name, int name_cap);
+/* Which conv kernel did the calling thread's last stand-alone conv entry point launch (odt_op_conv2d, odt_op_conv2d_cat,
+ * odt_op_se_tail's conv3; odt_op_bottleneck_tail, odt_op_bottleneck_block and odt_op_stem: the last conv launch of the call,
+ * with fuse = 1 the fused record)?  out[ODT_CONV_CHOICE_OUT] and name as odt_op_conv_choice fills them, from the finished
+ * record at its launch point; an error before any such call.  Host only; odt_forward does not record here (odt_describe
+ * lists a plan's rows). */
+int odt_op_last_conv(int* out, char* name, int name_cap);
 /* image preprocess (models.py:340-355) + zero pad -> [B,Hp,Wp,4] */
 int odt_op_preprocess(int device, const void* frames, int dtype, int B, int H,
                       int W, int pad_t, int pad_l, int Hp, int Wp, float* out);

@@ -106,7 +106,7 @@ class OdtLib(object):
       "odt_forward_async", "odt_synchronize", "odt_read_outputs", "odt_describe", "odt_range_health", "odt_submit", "odt_submit_ex", "odt_collect",
       "odt_ingest_buffer", "odt_set_source_size", "odt_tap", "odt_profile_enable",
       "odt_profile_read", "odt_profile_layer", "odt_probe_mfma_bf16", "odt_nn_cosine", "odt_op_conv2d", "odt_op_conv2d_cat",
-      "odt_op_bottleneck_tail", "odt_op_bottleneck_block", "odt_op_stem", "odt_op_conv_choice", "odt_op_preprocess",
+      "odt_op_bottleneck_tail", "odt_op_bottleneck_block", "odt_op_stem", "odt_op_conv_choice", "odt_op_last_conv", "odt_op_preprocess",
       "odt_op_maxpool", "odt_op_topk", "odt_op_nms", "odt_op_proposals",
       "odt_op_roi_align", "odt_op_detections", "odt_op_class_nms",
       "odt_op_dwconv", "odt_op_se_gate", "odt_op_rse_gate", "odt_op_rse_apply", "odt_op_se_tail", "odt_op_group_conv", "odt_op_bifpn_fuse", "odt_op_mbconv_expand_dw", "odt_op_effdet_post",
@@ -163,6 +163,7 @@ class OdtLib(object):
     d.odt_op_bottleneck_block.argtypes = [C.c_int, c_float_p] + [C.c_int] * 4 + [c_float_p] * 6 + [C.c_int, c_float_p]
     d.odt_op_stem.argtypes = [C.c_int, c_float_p] + [C.c_int] * 3 + [c_float_p, c_float_p, C.c_int, C.c_int, c_float_p]
     d.odt_op_conv_choice.argtypes = [c_int_p, C.c_int, C.c_int, c_int_p, C.c_char_p, C.c_int]
+    d.odt_op_last_conv.argtypes = [c_int_p, C.c_char_p, C.c_int]
     d.odt_op_preprocess.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 8 + [c_float_p]
     d.odt_op_maxpool.argtypes = [C.c_int, c_float_p] + [C.c_int] * 4 + [c_float_p]
     d.odt_op_topk.argtypes = [C.c_int, c_float_p, C.c_int, C.c_int, c_int_p]

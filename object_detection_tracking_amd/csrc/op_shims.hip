@@ -28,6 +28,25 @@ int set_dev(int device) {
   return 0;
 }
 
+// what the stand-alone conv entry points launched last on this thread (odt_op_last_conv): the finished record's row and
+// launch choices, kept at the launch points below.  Host only; nothing on the plan's path writes or reads it.
+struct LastConv { int variant = CV_NONE, splitk = 0, reduce_blocks = 0; };
+thread_local LastConv g_last_conv;
+void note_conv(const ConvParams& q) { g_last_conv.variant = q.variant; g_last_conv.splitk = q.splitk; g_last_conv.reduce_blocks = q.reduce_blocks; }
+
+// the ODT_CONV_CHOICE_OUT fields and the row name of a finished record (odt_op_conv_choice, odt_op_last_conv)
+void conv_report(int variant, int splitk, int reduce_blocks, int* out, char* name, int name_cap) {
+  const ConvKernelRow& r = conv_variant_row(variant);
+  for (int i = 0; i < ODT_CONV_CHOICE_OUT; ++i) out[i] = 0;
+  if (name && name_cap > 0) { std::strncpy(name, r.name, name_cap - 1); name[name_cap - 1] = 0; }
+  if (r.family != CF_F32) {
+    out[0] = 1; out[1] = r.family; out[2] = r.bm; out[3] = r.bn; out[4] = (r.flags & CVF_KWR) ? 1 : 0; out[5] = splitk;
+    out[6] = (r.flags & CVF_DSTAGE) ? 1 : 0; out[10] = reduce_blocks;
+  } else {
+    out[7] = r.bn == 128 ? 3 : (r.bm == 64 ? 2 : 1); out[8] = (r.flags & CVF_ST2) ? 2 : 1; out[9] = (r.flags & CVF_FINE) ? 1 : 0;
+  }
+}
+
 // one stand-alone conv (odt_op_conv2d*: dense tensors, null stream) as a plan would run it: the library's policy under the
 // call's knobs, a temporary weight image / split-K scratch / input range where the split kernels take it, a finished record
 int run_conv(ConvParams q, const Knobs& kn) {
@@ -69,6 +88,7 @@ int run_conv(ConvParams q, const Knobs& kn) {
     q.partial = tmp.partial;
   }
   if (conv_finish(q, kn)) return 1;
+  note_conv(q);
   ODT_HIP(hipMalloc((void**)&tmp.rec, sizeof(ConvParams)));
   ODT_HIP(hipMemcpy(tmp.rec, &q, sizeof(ConvParams), hipMemcpyHostToDevice));
   return launch_conv(q, tmp.rec, nullptr);
@@ -359,10 +379,12 @@ int odt_op_bottleneck_tail(int device, const float* in, int B, int H, int W, int
     a.out = nullptr; a.out_amax = nullptr;
     ConvParams recs[2] = {a, b};
     if (conv_check(a) || rec.put(recs)) return 1;
+    note_conv(a);
     if (launch_conv(a, rec.d, nullptr)) return 1;
   } else {
     ConvParams recs[2] = {a, b};
     if (conv_check(a) || conv_check(b) || rec.put(recs)) return 1;
+    note_conv(b);
     if (launch_conv(a, rec.d, nullptr) || launch_conv(b, rec.d + 1, nullptr)) return 1;
   }
   ODT_HIP(hipDeviceSynchronize());
@@ -441,6 +463,7 @@ int odt_op_bottleneck_block(int device, const float* x, int B, int H, int W, int
     if (trace) { if (tr.alloc(ntile * 16) || tr.zero()) return 1; a.trace = tr.d; }
     ConvParams recs[3] = {a, c1, b};
     if (conv_check(a) || rec.put(recs)) return 1;
+    note_conv(a);
     if (launch_bottleneck_block(a, rec.d, nullptr)) return 1;
     if (trace) {
       ODT_HIP(hipDeviceSynchronize());
@@ -461,6 +484,7 @@ int odt_op_bottleneck_block(int device, const float* x, int B, int H, int W, int
   } else {
     ConvParams recs[3] = {c1, a, b};
     if (conv_check(c1) || conv_check(a) || conv_check(b) || rec.put(recs)) return 1;
+    note_conv(b);
     if (launch_conv(c1, rec.d, nullptr) || launch_conv(a, rec.d + 1, nullptr) || launch_conv(b, rec.d + 2, nullptr)) return 1;
   }
   ODT_HIP(hipDeviceSynchronize());
@@ -501,9 +525,13 @@ int odt_op_stem(int device, const float* frame_pad, int B, int Hp, int Wp, const
     ODT_CHECK(conv_stem_fits(p), "odt_op_stem: shape not taken by the stem kernel");
     p.out = dout.d; p.out_H = Hq; p.out_W = Wq; conv_use_variant(p, CV_H2_STEM);
     if (grid > 0) p.debug |= (grid & 0x3ff) << 20;
-    if (conv_check(p) || rec.put(&p) || launch_conv(p, rec.d, nullptr)) return 1;
+    if (conv_check(p) || rec.put(&p)) return 1;
+    note_conv(p);
+    if (launch_conv(p, rec.d, nullptr)) return 1;
   } else {
-    if (conv_check(p) || rec.put(&p) || launch_conv(p, rec.d, nullptr)) return 1;
+    if (conv_check(p) || rec.put(&p)) return 1;
+    note_conv(p);
+    if (launch_conv(p, rec.d, nullptr)) return 1;
     if (launch_maxpool3x3s2(dmap.d, B, Ho0, Wo0, 64, dout.d, Hq, Wq, nullptr)) return 1;
   }
   ODT_HIP(hipDeviceSynchronize());
@@ -547,14 +575,17 @@ int odt_op_conv_choice(const int* shape, int conv_arith, int conv_split_family, 
     if (conv_split_partial_bytes(q) > 0) q.partial = ph_f;
   }
   if (conv_finish(q, kn)) { out[0] = 2; return 0; }
-  const ConvKernelRow& r = conv_variant_row(q.variant);
-  if (name && name_cap > 0) { std::strncpy(name, r.name, name_cap - 1); name[name_cap - 1] = 0; }
-  if (r.family != CF_F32) {
-    out[0] = 1; out[1] = r.family; out[2] = r.bm; out[3] = r.bn; out[4] = (r.flags & CVF_KWR) ? 1 : 0; out[5] = q.splitk;
-    out[6] = (r.flags & CVF_DSTAGE) ? 1 : 0; out[10] = q.reduce_blocks;
-  } else {
-    out[7] = r.bn == 128 ? 3 : (r.bm == 64 ? 2 : 1); out[8] = (r.flags & CVF_ST2) ? 2 : 1; out[9] = (r.flags & CVF_FINE) ? 1 : 0;
-  }
+  conv_report(q.variant, q.splitk, q.reduce_blocks, out, name, name_cap);
+  return 0;
+}
+
+// Which kernel did the last stand-alone conv call of this thread launch (odt_op_conv2d, odt_op_conv2d_cat, odt_op_se_tail's
+// conv3; odt_op_bottleneck_tail, odt_op_bottleneck_block and odt_op_stem: the LAST conv launch of the call -- the fused record
+// with fuse = 1)?  The fields of odt_op_conv_choice, taken from the finished record at its launch point.  Host only.
+int odt_op_last_conv(int* out, char* name, int name_cap) {
+  ODT_CHECK(out, "odt_op_last_conv: null argument");
+  ODT_CHECK(g_last_conv.variant != CV_NONE, "odt_op_last_conv: this thread has launched no stand-alone conv yet");
+  conv_report(g_last_conv.variant, g_last_conv.splitk, g_last_conv.reduce_blocks, out, name, name_cap);
   return 0;
 }
 

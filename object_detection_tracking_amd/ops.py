@@ -117,6 +117,17 @@ def conv_choice(shape, conv_arith=0, conv_split_family=0, lib=None):
   return d
 
 
+def last_conv(lib):
+  """odt_op_last_conv: the kernel the calling thread's last stand-alone conv call (conv2d, conv2d_cat, bottleneck_tail,
+  bottleneck_block, stem) launched on `lib` -- the CONV_CHOICE_OUT fields and the row's name, as conv_choice returns them."""
+  out = np.zeros(len(CONV_CHOICE_OUT), np.int32)
+  name = C.create_string_buffer(64)
+  lib.check(lib.dll.odt_op_last_conv(iptr(out), name, 64))
+  d = dict(zip(CONV_CHOICE_OUT, (int(v) for v in out)))
+  d["name"] = name.value.decode()
+  return d
+
+
 def preprocess(frames, pad_t, pad_l, Hp, Wp, lib=None, device=0):
   """reference models.py:340-355 + zero pad; returns [B,Hp,Wp,4]."""
   lib = _L(lib)

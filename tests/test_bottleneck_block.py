@@ -91,7 +91,12 @@ def test_bottleneck_block_fused_vs_f64(backend, shape):
   (b) the two forms agree within the same margin."""
   name, lib = backend
   x, wts, ref, mag = _case(shape)
-  got = {f: ops.bottleneck_block(x, *wts, fuse=f, lib=lib) for f in (False, True)}
+  got = {}
+  for f in (False, True):
+    got[f] = ops.bottleneck_block(x, *wts, fuse=f, lib=lib)
+    # the record odt_op_bottleneck_block launched last: conv_block_kernel runs conv2's fused-tail record | conv3's own launch
+    got_row = ops.last_conv(lib)
+    assert (got_row["name"], got_row["splitk"]) == (("H2KF_256x64", 1) if f else ("H2_256x256", 1)), got_row
   e0 = float((np.abs(got[False] - ref) / mag).max())
   e1 = float((np.abs(got[True] - ref) / mag).max())
   d01 = float((np.abs(got[True] - got[False]) / mag).max())

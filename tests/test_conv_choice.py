@@ -10,7 +10,8 @@ odt_op_conv_choice entry point and printed the finished records of whole plans -
            the families, exact f32, every knob of conv_policy_with_knobs / conv_select at a non-default value, the exact-f32
            instantiations, the SPLIT_PIPES of test_ops.py).
 A policy or kernel change shows up here as a diff of the fixture, to be reviewed.  The mapping fields -> kernel is not
-in the fixture (the parent had no row names): the numerical op tests cover it.
+in the fixture (the parent had no row names): tests/test_conv_rows.py runs every selectable row by name and checks, per
+launch, that odt_op_conv_choice's fields and name are those of the record that was launched (ops.last_conv).
 """
 import json
 import os

@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as TF
 
 from common import torch_conv_nhwc
+from conv_rows import assert_choice_agrees, assert_row, conv_shape
 from object_detection_tracking_amd import ops
 from object_detection_tracking_amd._lib import ODT_GRAPH_MULTI, ODT_GRAPH_SINGLE
 from oracle import graph as og
@@ -44,6 +45,7 @@ def _run_conv(lib, case, rng, tile_env=None):
   w = (rng.standard_normal((k, k, Cin, Cout)) * np.sqrt(2.0 / (k * k * Cin))).astype(F)
   b = rng.standard_normal(Cout).astype(F)
   y = ops.conv2d(x, w, b, s, d, pt, pl, (Ho, Wo), relu=relu, lib=lib)
+  assert_choice_agrees(lib, conv_shape(B, H, W, Cin, Cout, k, s, d, pt, pl, Ho, Wo))      # the launch is what odt_op_conv_choice reports
   # against float64, relative to the magnitude the sum was formed from: |y - y64| <= 5e-6 * (sum |a||w| + |bias|) -- what
   # the f64 tests of the split kernels justify (test_parity_report.py: 1.6e-7 ... 4.2e-7 measured); ReLU is 1-Lipschitz
   r = torch_conv_nhwc(x, w, b, s, d, pt, pl, Ho, Wo, dtype=np.float64)
@@ -486,6 +488,7 @@ def _fuzz_case(rng, lib, big, couts=None):
     want = np.maximum(want, 0)
   got = ops.conv2d(x, w, b, stride=stride, dil=dil, pad_t=pad_t, pad_l=pad_l, out_hw=(Ho, Wo),
                    out_off=(oy, ox), res=res, res_mode=res_mode, relu=relu, lib=lib)
+  assert_choice_agrees(lib, conv_shape(B, H, W, Cin, Cout, k, stride, dil, pad_t, pad_l, Ho, Wo, res_mode=res_mode))
   assert np.all(got[:, :oy] == 0) and np.all(got[:, :, :ox] == 0)
   np.testing.assert_allclose(got[:, oy:, ox:], want, rtol=2e-4, atol=2e-4)
 
@@ -520,6 +523,7 @@ def test_conv_two_sources(backend, monkeypatch):
       bias = rng.standard_normal((Cout,)).astype(np.float32)
       want = a @ wa + b2[:, ::stride_b, ::stride_b][:, :Ho, :Wo] @ wb + bias
       got = ops.conv2d_cat(a, b2, wa, wb, bias, stride_b=stride_b, relu=True, lib=lib)
+      assert_choice_agrees(lib, conv_shape(B, Ho, Wo, Ca, Cout, 1, 1, 1, 0, 0, Ho, Wo, cin2=Cb))
       np.testing.assert_allclose(got, np.maximum(want, 0), rtol=2e-4, atol=2e-4)
 
 
@@ -624,6 +628,7 @@ def test_conv2d_fp16x2_dynamic_range(backend, monkeypatch):
   w = (rng.standard_normal((1, 1, K, N)) * np.sqrt(2.0 / K)).astype(F)
   b = np.zeros(N, F)
   y = ops.conv2d(x, w, b, 1, 1, 0, 0, (G, 40), lib=lib)
+  assert_row(lib, "H2_256x256", 1)      # conv_h2_kernel on 256 x 256 tiles (M = 320: two tiles)
   ref = x.astype(np.float64) @ w[0, 0].astype(np.float64)
   mag = np.abs(x.astype(np.float64)) @ np.abs(w[0, 0].astype(np.float64))
   wsum = np.abs(w[0, 0].astype(np.float64)).sum(axis=0)
@@ -643,13 +648,18 @@ def test_conv2d_fp16x2_power_of_two_equivariance(backend, pipe, monkeypatch):
   name, lib = backend
   _split_env(monkeypatch, pipe)
   rng = np.random.default_rng(31)
-  x = rng.standard_normal((2, 13, 15, 64)).astype(F)
+  # ("2/256" at 16 x 17 = 272 pixels per image: the kw-reuse kernel takes a layer from 256 on -- at 13 x 15 "2/256" and
+  # "2/256/nokwr" both run conv_h2_kernel; at 272 "2/128" would run the kw-reuse kernel's 256 x 128 tiles too)
+  row, (Hx, Wx) = {"2/256": ("H2K_256x256", (16, 17)), "2/256/nokwr": ("H2_256x256", (13, 15)), "2/128": ("H2_128x128", (13, 15))}[pipe]
+  x = rng.standard_normal((2, Hx, Wx, 64)).astype(F)
   w = (rng.standard_normal((3, 3, 64, 256)) * 0.05).astype(F)
   b = np.zeros(256, F)
-  y0 = ops.conv2d(x, w, b, 1, 1, 1, 1, (13, 15), lib=lib)
+  y0 = ops.conv2d(x, w, b, 1, 1, 1, 1, (Hx, Wx), lib=lib)
+  assert_row(lib, row, 1)
   assert np.isfinite(y0).all() and np.abs(y0).max() > 0
   for k in (-40, -7, 5, 40):
-    yk = ops.conv2d(x * F(2.0 ** k), w, b, 1, 1, 1, 1, (13, 15), lib=lib)
+    yk = ops.conv2d(x * F(2.0 ** k), w, b, 1, 1, 1, 1, (Hx, Wx), lib=lib)
+    assert_row(lib, row, 1)
     assert np.array_equal(yk, y0 * F(2.0 ** k)), k
 
 
@@ -662,12 +672,14 @@ def test_conv2d_split_output_offset_and_residual(backend, pipe, monkeypatch):
   w = (rng.standard_normal((3, 3, 64, 256)) * 0.05).astype(F)
   b = rng.standard_normal(256).astype(F)
   got = ops.conv2d(x, w, b, 1, 1, 1, 1, (10, 12), out_off=(1, 1), relu=True, lib=lib)
+  assert_choice_agrees(lib, conv_shape(1, 10, 12, 64, 256, 3, 1, 1, 1, 1, 10, 12))
   want = np.maximum(torch_conv_nhwc(x, w, b, 1, 1, 1, 1, 10, 12), 0)
   assert np.all(got[:, :1] == 0) and np.all(got[:, :, :1] == 0)
   np.testing.assert_allclose(got[:, 1:, 1:], want, rtol=1e-4, atol=1e-4)
   # same-shape residual (added in the epilogue by conv_split3_kernel, accumulator start value in the older loops)
   res = rng.standard_normal((1, 10, 12, 256)).astype(F)
   got = ops.conv2d(x, w, b, 1, 1, 1, 1, (10, 12), res=res, res_mode=1, relu=True, lib=lib)
+  assert_choice_agrees(lib, conv_shape(1, 10, 12, 64, 256, 3, 1, 1, 1, 1, 10, 12, res_mode=1))
   np.testing.assert_allclose(got, np.maximum(torch_conv_nhwc(x, w, b, 1, 1, 1, 1, 10, 12) + res, 0),
                              rtol=1e-4, atol=1e-4)
 
@@ -684,16 +696,19 @@ def test_conv2d_split_residual_bottleneck_conv3(backend, pipe, monkeypatch):
   b = rng.standard_normal(512).astype(F)
   res = rng.standard_normal((2, 9, 11, 512)).astype(F)
   got = ops.conv2d(x, w, b, res=res, res_mode=1, relu=True, lib=lib)
+  assert_choice_agrees(lib, conv_shape(2, 9, 11, 256, 512, 1, 1, 1, 0, 0, 9, 11, res_mode=1))
   want = np.maximum(torch_conv_nhwc(x, w, b, 1, 1, 0, 0, 9, 11) + res, 0)
   np.testing.assert_allclose(got, want, rtol=1e-4, atol=1e-4)
   for cout in (128, 64):               # the 256 x 128 and 256 x 64 tiles
     w2 = (rng.standard_normal((1, 1, 256, cout)) / 16).astype(F)
     r2 = rng.standard_normal((2, 9, 11, cout)).astype(F)
     got = ops.conv2d(x, w2, b[:cout], res=r2, res_mode=1, relu=True, lib=lib)
+    assert_choice_agrees(lib, conv_shape(2, 9, 11, 256, cout, 1, 1, 1, 0, 0, 9, 11, res_mode=1))
     want = np.maximum(torch_conv_nhwc(x, w2, b[:cout], 1, 1, 0, 0, 9, 11) + r2, 0)
     np.testing.assert_allclose(got, want, rtol=1e-4, atol=1e-4)
   up = rng.standard_normal((2, 5, 6, 512)).astype(F)
   got = ops.conv2d(x, w, b, res=up, res_mode=2, lib=lib)
+  assert_choice_agrees(lib, conv_shape(2, 9, 11, 256, 512, 1, 1, 1, 0, 0, 9, 11, res_mode=2))
   want = torch_conv_nhwc(x, w, b, 1, 1, 0, 0, 9, 11) + np.repeat(np.repeat(up, 2, 1), 2, 2)[:, :9, :11]
   np.testing.assert_allclose(got, want, rtol=1e-4, atol=1e-4)
 
@@ -715,6 +730,7 @@ def test_conv2d_split_two_sources(backend, pipe, monkeypatch):
     bias = rng.standard_normal((Cout,)).astype(F)
     want = a @ wa + b2[:, ::stride_b, ::stride_b][:, :Ho, :Wo] @ wb + bias
     got = ops.conv2d_cat(a, b2, wa, wb, bias, stride_b=stride_b, relu=True, lib=lib)
+    assert_choice_agrees(lib, conv_shape(B, Ho, Wo, Ca, Cout, 1, 1, 1, 0, 0, Ho, Wo, cin2=Cb))
     np.testing.assert_allclose(got, np.maximum(want, 0), rtol=2e-4, atol=2e-4)
 
 
@@ -742,6 +758,7 @@ def test_conv2d_split_16wide_stage_extras(backend, pipe, monkeypatch):
   b = rng.standard_normal(256).astype(F)
   res = rng.standard_normal((2, 9, 11, 256)).astype(F)
   got = ops.conv2d(x, w, b, res=res, res_mode=1, relu=True, lib=emu_lib)
+  assert_choice_agrees(emu_lib, conv_shape(2, 9, 11, 96, 256, 1, 1, 1, 0, 0, 9, 11, res_mode=1))
   np.testing.assert_allclose(got, np.maximum(torch_conv_nhwc(x, w, b, 1, 1, 0, 0, 9, 11) + res, 0), rtol=1e-4, atol=1e-4)
   a = rng.standard_normal((2, 9, 11, 64)).astype(F)
   b2 = rng.standard_normal((2, 18, 21, 160)).astype(F)
@@ -749,6 +766,7 @@ def test_conv2d_split_16wide_stage_extras(backend, pipe, monkeypatch):
   wb = (rng.standard_normal((160, 256)) / 12).astype(F)
   want = a @ wa + b2[:, ::2, ::2][:, :9, :11] @ wb + b
   got = ops.conv2d_cat(a, b2, wa, wb, b, stride_b=2, relu=False, lib=emu_lib)
+  assert_choice_agrees(emu_lib, conv_shape(2, 9, 11, 64, 256, 1, 1, 1, 0, 0, 9, 11, cin2=160))
   np.testing.assert_allclose(got, want, rtol=2e-4, atol=2e-4)
 
 
@@ -784,7 +802,10 @@ def test_stem_kernel_vs_two_launches_and_f64(backend, case):
   x = rng.uniform(-2.2, 2.7, (B, Hp, Wp, 3)).astype(F)         # (the normalised pixel range of build_preprocess)
   w = (rng.standard_normal((7, 7, 3, 64)) * np.sqrt(2.0 / 147)).astype(F)
   b = (rng.standard_normal(64) * 0.1).astype(F)
-  got = {f: ops.stem(x, w, b, fuse=f, grid=grid, lib=lib) for f in (False, True)}
+  got = {}
+  for f in (False, True):
+    got[f] = ops.stem(x, w, b, fuse=f, grid=grid, lib=lib)
+    assert_row(lib, "H2_STEM" if f else "H2_128x64", 1)      # conv_stem_kernel | conv_h2_kernel (+ maxpool3x3s2_kernel)
   np.testing.assert_array_equal(got[True], got[False])
   xt = torch.from_numpy(x.astype(np.float64)).permute(0, 3, 1, 2)
   wt = torch.from_numpy(w.astype(np.float64)).permute(3, 2, 0, 1)
@@ -805,6 +826,7 @@ BOTTLENECK_CASES = [
     (2, 9, 17, 128, 1, True, True),       # a tile that crosses the image boundary (two runs), odd sizes
     (1, 16, 16, 192, 2, False, False),    # dilation 2, six 32-column chunks, no residual, no activation
 ]
+assert {c[7] if len(c) > 7 else 256 for c in BOTTLENECK_CASES} == {64, 128, 256}      # each fused-tail row (H2KF_256x64 / x128 / x256) runs
 
 
 @pytest.mark.parametrize("case", BOTTLENECK_CASES)
@@ -827,6 +849,9 @@ def test_bottleneck_tail_fused_vs_f64(backend, case):
   got = {}
   for fuse in (False, True):
     got[fuse] = ops.bottleneck_tail(x, w2, b2, w3, b3, res=res, dil=dil, relu3=relu3, fuse=fuse, lib=lib)
+    if fuse:      # the one launch: the fused-tail row of conv2's width
+      assert C in (64, 128, 256)
+      assert_row(lib, "H2KF_256x%d" % C, 1)
     err = np.abs(got[fuse] - ref) / mag
     assert err.max() < 4e-7, (fuse, err.max())
   assert np.max(np.abs(got[True] - got[False]) / mag) < 3e-7
@@ -871,11 +896,13 @@ def test_conv2d_fp16x2_512x64_tile(backend, monkeypatch):
   for mode in ("0", "2"):
     monkeypatch.setenv("ODT_CONV_H2_N64_BM512", mode)
     out[mode] = ops.conv2d(x, w, b, 1, 1, 1, 1, (H, W), relu=True, lib=lib)
+    assert_row(lib, "H2K_512x64" if mode == "2" else "H2K_256x64", 1)
     np.testing.assert_allclose(out[mode], ref, rtol=1e-4, atol=1e-4)
   assert np.array_equal(out["0"], out["2"])
   # dilation 2 (the other halo width)
   monkeypatch.setenv("ODT_CONV_H2_N64_BM512", "2")
   y = ops.conv2d(x, w, b, 1, 2, 2, 2, (H, W), relu=False, lib=lib)
+  assert_row(lib, "H2K_512x64", 1)
   np.testing.assert_allclose(y, torch_conv_nhwc(x, w, b, 1, 2, 2, 2, H, W), rtol=1e-4, atol=1e-4)
 
 
@@ -902,6 +929,7 @@ def test_conv2d_fp16x2_512x64_tile_generic_kernel(backend, case, monkeypatch):
   for mode in ("0", "2"):
     monkeypatch.setenv("ODT_CONV_H2_N64_BM512", mode)
     out[mode] = ops.conv2d(x, w, b, stride, dil, pt, pl, (Ho, Wo), relu=relu, lib=lib)
+    assert_row(lib, "H2_512x64" if mode == "2" else "H2_128x64", 1)
     np.testing.assert_allclose(out[mode], ref, rtol=1e-4, atol=1e-4)
   if k > 1:
     assert np.array_equal(out["0"], out["2"])
@@ -912,18 +940,26 @@ def test_conv2d_fp16x2_512x64_tile_generic_kernel(backend, case, monkeypatch):
 @pytest.mark.parametrize("case", [
     (1, 10, 15, 512, 256, 1, 1, 1, 0, 0, 10, 15, True),      # dense 1x1, M = 150: 3 x 2 tiles of 64 x 128 (res4 conv1 at b = 1)
     (1, 10, 15, 256, 512, 1, 1, 1, 0, 0, 10, 15, False),     # dense 1x1, short reduction, several n-tiles (res4 conv3 at b = 1)
-    (1, 9, 15, 64, 128, 1, 1, 1, 0, 0, 9, 15, True),         # dense 1x1, K = 64: below conv_h2d_kernel's two double stages, conv_h2_kernel under both settings
+    (1, 9, 15, 64, 128, 1, 1, 1, 0, 0, 9, 15, True),         # dense 1x1, K = 64: below conv_h2d_kernel's two double stages, conv_h2_kernel under both settings (M = 135: 3 tiles of 64 rows)
     (1, 9, 15, 128, 128, 1, 1, 1, 0, 0, 9, 15, True),        # dense 1x1, K = 128: exactly two double stages (the peeled steps only, no steady-state step)
     (1, 10, 15, 64, 256, 3, 1, 1, 1, 1, 10, 15, True),       # 3x3 taps on the generic kernel
     (1, 20, 15, 64, 128, 1, 2, 1, 0, 0, 10, 8, False),       # strided, one n-tile, a partial last tile (M = 80)
 ])
 def test_conv2d_fp16x2_64x128_tile_without_splitk(backend, case, monkeypatch):
   """conv_h2_kernel<2, 1>: layers whose 128 x 128 tiles cannot fill the chip but whose 64 x 128 ones can (b = 1 below res3)
-  run on two-wave 64 x 128 tiles WITHOUT split-K (no partial slabs, no combine pass); the residual path too."""
+  run on two-wave 64 x 128 tiles WITHOUT split-K (no partial slabs, no combine pass); the residual path too.  Every call
+  asserts the row it launched (ops.last_conv): H2_128x128 | H2_64x128 | H2_64x64, and H2D_64x128 | H2D_64x64 where the
+  double-stage kernel takes the reduction."""
   name, lib = backend
-  _split_env(monkeypatch, "2")
-  monkeypatch.setenv("ODT_CONV_SPLIT3_MINTILES", "3")     # (test sizes: t128 = 2 .. 2 < 3 <= t64)
+  _split_env(monkeypatch, "2/128")      # (ODT_CONV_SPLIT3_BM=128: the fit is 128-row tiles whatever the layer's size -- at these
+  # sizes split3_fit finds none for the short reductions, K / 16 stages do not cut into ranges of eight, and SPLIT1_256x128 ran)
   B, H, W, Cin, Cout, k, stride, dil, pt, pl, Ho, Wo, relu = case
+  # "the 128-row tiles do not fill the chip, the 64-row ones do" (rule_h2_64_rows counts 128 x 128 and 64 x 128 tiles):
+  # t128 < MINTILES <= t64 -- t128 / t64 = 4 / 6, 8 / 12, 2 / 3, 2 / 3, 4 / 6, 1 / 2 for the six cases
+  t128 = -(-(B * Ho * Wo) // 128) * -(-Cout // 128)
+  t64 = -(-(B * Ho * Wo) // 64) * -(-Cout // 128)
+  assert t128 < t128 + 1 <= t64
+  monkeypatch.setenv("ODT_CONV_SPLIT3_MINTILES", str(t128 + 1))
   rng = np.random.default_rng(66)
   x = rng.standard_normal((B, H, W, Cin)).astype(F)
   w = (rng.standard_normal((k, k, Cin, Cout)) * 0.05).astype(F)
@@ -932,18 +968,19 @@ def test_conv2d_fp16x2_64x128_tile_without_splitk(backend, case, monkeypatch):
   ref = torch_conv_nhwc(x, w, b, stride, dil, pt, pl, Ho, Wo) + res
   if relu:
     ref = np.maximum(ref, 0)
+  rows = {"0": "H2_128x128", "1": "H2_64x128", "3": "H2_64x64"}      # (0: the tiles the layer has without the knob, split-K where the policy cuts)
+  monkeypatch.setenv("ODT_CONV_H2_BK64", "0")      # conv_h2_kernel, as the title says; the double-stage kernel below
   out = {}
   for mode in ("0", "1", "3"):              # (3: 64 x 64 tiles, conv_h2_kernel<1, 1>)
     monkeypatch.setenv("ODT_CONV_H2_BM64", mode)
     out[mode] = ops.conv2d(x, w, b, stride, dil, pt, pl, (Ho, Wo), res=res, res_mode=1, relu=relu, lib=lib)
+    assert_row(lib, rows[mode], None if mode == "0" else 1)
     np.testing.assert_allclose(out[mode], ref, rtol=1e-4, atol=2e-4)
   for mode in ("1", "3"):
     np.testing.assert_allclose(out["0"], out[mode], rtol=0, atol=3e-6 * float(np.abs(ref).max()))
   # the dense 1x1 reductions take conv_h2d_kernel (double stages: two BK = 32 sub-stages per barrier, round 5) on these tiles;
   # ODT_CONV_H2_BK64=0 keeps conv_h2_kernel: the same products in another slice order -> equal at f32 rounding level
   if k == 1 and stride == 1 and Cin % 64 == 0:
-    t128 = -(-(B * Ho * Wo) // 128) * -(-Cout // 128)
-    monkeypatch.setenv("ODT_CONV_SPLIT3_MINTILES", str(t128 + 1))    # (the 128-row tiles do not "fill the chip", the 64-row ones do)
     r64 = torch_conv_nhwc(x, w, b, stride, dil, pt, pl, Ho, Wo, dtype=np.float64) + res
     if relu:
       r64 = np.maximum(r64, 0)
@@ -953,10 +990,10 @@ def test_conv2d_fp16x2_64x128_tile_without_splitk(backend, case, monkeypatch):
       for bk in ("1", "0"):
         monkeypatch.setenv("ODT_CONV_H2_BK64", bk)
         both[bk] = ops.conv2d(x, w, b, stride, dil, pt, pl, (Ho, Wo), res=res, res_mode=1, relu=relu, lib=lib)
+        # (the double-stage kernel really ran: K = 64 is below its two double stages and stays on conv_h2_kernel)
+        assert_row(lib, rows[mode].replace("H2_", "H2D_") if bk == "1" and Cin >= 128 else rows[mode], 1)
         assert np.abs(both[bk] - r64).max() <= 4e-6 * float(np.abs(r64).max()), (mode, bk)
       np.testing.assert_allclose(both["1"], both["0"], rtol=0, atol=3e-6 * float(np.abs(ref).max()))
-      if Cin >= 256:
-        assert not np.array_equal(both["1"], both["0"]), mode   # (another summation order: the double-stage kernel really ran)
 
 
 @pytest.mark.parametrize("case", [
@@ -982,5 +1019,9 @@ def test_conv2d_fp16x2_kw_reuse_kernel_with_splitk(backend, case, monkeypatch):
   for mode in ("0", "1"):
     monkeypatch.setenv("ODT_CONV_H2K_SPLITK", mode)
     out[mode] = ops.conv2d(x, w, b, stride, dil, pt, pl, (Ho, Wo), relu=relu, lib=lib)
+    if mode == "1":      # the kw-reuse kernel, the groups cut in two | "0": the generic kernel's 128 x 128 tiles (10 of them: whole reductions)
+      assert_row(lib, "H2K_256x128", 2)
+    else:
+      assert_row(lib, "H2_128x128", 1)
     np.testing.assert_allclose(out[mode], ref, rtol=1e-4, atol=2e-4)
   np.testing.assert_allclose(out["0"], out["1"], rtol=0, atol=3e-6 * float(np.abs(ref).max()))
