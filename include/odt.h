@@ -109,6 +109,12 @@ typedef struct odt_config {
                              * 512 channels; dilations ignored) | 2 resnext_32x4d_bottleneck (--use_resnext: conv1 1x1 to 2 ch, conv2
                              * 3x3 in 32 groups with stride and dilation 'SAME' (W [3,3,2ch/32,2ch]), conv3 1x1 to 4 ch).  Neither
                              * 1 nor 2 combines with use_se */
+  int32_t use_deformable;   /* --use_deformable (nn.py:469-485, 574-585): the stride-2 bottleneck that opens group 1, 2 or 3 runs a
+                             * deformable conv2 where block 0 is among the group's last three blocks (num_blocks[g] <= 3; R50 / R101 /
+                             * R152: group3/block0 alone).  Variables groupG/block0/conv2_offset/{W [3,3,C,18], b [18]} (even channels
+                             * row offsets, odd ones column offsets, tap-major) and conv2/W [3,3,C,C] without conv2/bn: the nine taps are
+                             * bilinear samples at clamped coordinates, each image with its own offsets.  block_kind 0 without use_se
+                             * only; not with use_dilations (the reference graph does not build) */
 } odt_config;
 
 /* conv_arith: all modes keep f32 tensors and f32 accumulation.  ODT_ARITH_F32: every product on the exact-f32 MFMA
@@ -492,6 +498,17 @@ int odt_op_se_tail(int device, const float* t2, int B, int H, int W, int ch, con
  * |max| the kernel recorded for out.  Plain f32, fixed summation order. */
 int odt_op_group_conv(int device, const float* x, int B, int H, int W, int C, const float* w, const float* bias, int stride,
                       int dil, int pad_t, int pad_l, int Ho, int Wo, int relu, float* out, float* amax);
+/* Deformable stage-entry conv2 (csrc/conv_deform.hip; nn.py:469-485, 1642-1712) as the plan runs it: x [B,H,W,C], C in {128, 256,
+ * 512}; w_off HWIO [3,3,C,18] + b_off [18]: conv2_offset evaluated at the even positions (3x3, stride 2, one zero row / column in
+ * front) -> offsets_out [B,Ho,Wo,18], Ho = ceil(H / 2), Wo = ceil(W / 2); w HWIO [3,3,C,C]: out[b,yo,xo,:] = sum over taps n = 3 ky +
+ * kx of the bilinear sample of x at (clip(2 yo - 1 + ky + off[2 n], 0, H - 1), clip(2 xo - 1 + kx + off[2 n + 1], 0, W - 1)) times
+ * w[ky][kx] -> out [B,Ho,Wo,C]; out_amax [1]: the |max| the kernel recorded for out.  Plain f32, fixed summation order. */
+int odt_op_deform_conv(int device, const float* x, int B, int H, int W, int C, const float* w_off, const float* b_off, const float* w,
+                       float* out, float* out_amax, float* offsets_out);
+/* The same on a pitched view, as the plan's Tensor::H / W / C against h / w: x is [B,Ha,Wa,ldc] (Ha >= H, Wa >= W, ldc >= C, ldc % 4 ==
+ * 0) and the op reads rows < H, columns < W, channels < C of it; nothing outside the view is touched. */
+int odt_op_deform_conv_view(int device, const float* x, int B, int Ha, int Wa, int ldc, int H, int W, int C, const float* w_off,
+                            const float* b_off, const float* w, float* out, float* out_amax, float* offsets_out);
 /* BiFPN node input fusion (launch_bifpn_fuse): n = 1..3 inputs ins[k] [B,in_hw[k][0],in_hw[k][1],ldc], mode[k] 0 same
  * size, 1 nearest resize, 2 3x3 / s2 'SAME' max pool with pads[k] = (top, left); wsm != NULL: 'fastattn' with the raw
  * WSM scalars [n], else a plain sum; act 0 / 2 (swish).  out [B,h,w,ldc]. */

@@ -427,6 +427,28 @@ size_t group_conv_weight_elems(int C);
 int group_conv_pack_weights(const float* hwio, const double* scale, int C, float* dst);
 int launch_group_conv(const GroupConvParams& p, hipStream_t stream);
 
+// ------------------------------------------------------- deformable 3x3 conv (conv_deform.hip; --use_deformable, reference nn.py:469-485)
+// off = conv2_offset(in) at the even positions (3x3, stride 2, one zero row / column in front, + bias), then out = the 3x3
+// stride-2 conv of in whose nine taps are bilinear samples at (tap position + off), coordinates clamped to the map.  in is a
+// pitched NHWC view; off and out are dense.  Plain f32 in a fixed order in every arithmetic mode; no bias / BN / activation.
+struct DeformConvParams {
+  const float* in;      // [B,Ha,Wa,ldc], logical [B,H,W,C]
+  const float* wt_off;  // deform_pack_offset_weights image
+  const float* b_off;   // [18]
+  const float* wt;      // deform_pack_weights image
+  float* off;           // [B,Ho,Wo,18]: (row, column) offset of tap n = 3 ky + kx at channels (2 n, 2 n + 1)
+  float* out;           // [B,Ho,Wo,C]
+  unsigned* out_amax;   // range slot of out (|max| of what is stored) or nullptr
+  int B, H, W, Ha, Wa, ldc, C, Ho, Wo;      // C in {128, 256, 512}; Ho = ceil(H / 2), Wo = ceil(W / 2)
+};
+size_t deform_offset_weight_elems(int C);
+size_t deform_weight_elems(int C);
+// HWIO [3][3][C][18] / [3][3][C][C] -> the kernels' images (host memory)
+int deform_pack_offset_weights(const float* hwio, int C, float* dst);
+int deform_pack_weights(const float* hwio, int C, float* dst);
+// both kernels, in stream order (`between`: an event recorded after the offset kernel, for profiling)
+int launch_deform_conv(const DeformConvParams& p, hipStream_t stream, hipEvent_t between = nullptr);
+
 // ------------------------------------------------------- EfficientDet tail (effdet_post.hip)
 struct EffPostParams {
   const float* cls[5];     // per level [B, npix, ldc_cls]  (9 * ncls valid channels: anchor-major)

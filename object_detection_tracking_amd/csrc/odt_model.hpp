@@ -60,11 +60,12 @@ struct ConvOp {
 
 enum OpKind { OP_PRE, OP_CONV, OP_POOL, OP_SUB2, OP_PROPOSALS, OP_ROI_HEAD, OP_DETECT, OP_ROI_FINAL,
               OP_ROI_MASK, OP_MASK_SELECT, OP_PRE_RGB, OP_DW, OP_CMEAN, OP_CSCALE, OP_FUSE, OP_EFF_POST, OP_ROI_EFF, OP_SE_GATE,
-              OP_SE_GATE_MEAN, OP_WSCALE, OP_MB_EXPAND_DW, OP_RSE_GATE, OP_RSE_APPLY, OP_GCONV, OP_BLOCK };
+              OP_SE_GATE_MEAN, OP_WSCALE, OP_MB_EXPAND_DW, OP_RSE_GATE, OP_RSE_APPLY, OP_GCONV, OP_BLOCK, OP_DCONV };
 struct Op {
   OpKind kind;
   int conv = -1;        // index into convs (OP_BLOCK: the block's conv2, whose record launches conv_block_kernel)
   int gconv = -1;       // OP_GCONV: its index among the plan's grouped convs (profiling events)
+  int dconv = -1;       // OP_DCONV: its index among the plan's deformable convs (profiling events)
   Tensor in, out;
   DwConvParams dw{};    // OP_DW
   MbExpandDwParams mb{};   // OP_MB_EXPAND_DW
@@ -73,6 +74,7 @@ struct Op {
   ResSeParams rse{};    // OP_RSE_GATE: pool of conv2's output + the SE-ResNet gate
   ResSeApplyParams rsa{};   // OP_RSE_APPLY: gate * conv3 + shortcut, ReLU
   GroupConvParams gc{};    // OP_GCONV: the ResNeXt block's 32-group 3x3 conv2 (conv_group.hip)
+  DeformConvParams dc{};   // OP_DCONV: a deformable stage entry's conv2_offset + deformable conv2 (conv_deform.hip)
   float* aux = nullptr; // OP_CMEAN: means out [B,ldc]; OP_CSCALE / OP_WSCALE: gates in [B,ldc]
   const float* wt0 = nullptr;   // OP_WSCALE: the conv's unscaled weights [Cout][K] (conv = index of the conv whose weights are rebuilt)
   float* aux2 = nullptr;   // OP_CMEAN: partial-sum scratch
@@ -131,6 +133,7 @@ struct odt_model {
   ConvPolicy policy{};               // conv arithmetic / kernel-family policy of this handle (attach_split_weights)
   int se_blocks = 0;                 // SE-ResNet (odt_config.use_se): bottlenecks that run pool + gate + apply (resnet_se.hip)
   int gconv_ops = 0;                 // ResNeXt (odt_config.block_kind == 2): launches of the 32-group 3x3 conv per forward (conv_group.hip)
+  int dconv_ops = 0;                 // odt_config.use_deformable: stage entries that run conv2_offset + the deformable conv2 (conv_deform.hip)
   int mb_fused = 0;                  // EfficientNet: MBConv blocks whose expand + depthwise run as one kernel (effnet_mbconv.hip)
   // tail overlap: the selection / ROIAlign / box-head / NMS kernels of forward i (a few dozen workgroups each,
   // ~2 ms per 8-frame step) run on a side stream under the backbone of forward i+1.  The next forward's FPN stage
@@ -177,6 +180,8 @@ struct odt_model {
   std::vector<double> prof_layer_ms;
   std::vector<hipEvent_t> ev_gconv;  // OP_GCONV i: events [2 i, 2 i + 1]
   double prof_gconv_ms = 0;
+  std::vector<hipEvent_t> ev_dconv;  // OP_DCONV i: events [3 i, 3 i + 2] (before, between the two kernels, after)
+  double prof_doff_ms = 0, prof_dconv_ms = 0;
   int prof_forwards = 0;
   int prof_launches = 0;
 
@@ -224,6 +229,7 @@ int upload_conv_cat(odt_model* m, const std::string& sa, int cin_a, const std::s
                     const float** wt_out, const float** bias_out);
 int upload_raw(odt_model* m, const std::vector<float>& v, const float** out);
 int upload_group_conv(odt_model* m, const std::string& scope, int C, const float** wt_out, const float** bias_out);
+int upload_deform_conv(odt_model* m, const std::string& pre, int C, const float** wt_off, const float** b_off, const float** wt);
 int upload_se_gate(odt_model* m, const std::string& pre, int ch, const float** w1, const float** b1, const float** w2t,
                    const float** b2);
 int add_conv(odt_model* m, const std::string& name, const Tensor& in, int cin, const float* wt, const float* bias, int kh,
@@ -280,6 +286,7 @@ void visit_op_ptrs(odt_model* m, size_t oi, F&& f) {
     case OP_RSE_GATE: f(op.rse.t2); f(op.rse.part); f(op.rse.mean); f(op.rse.rvec); f(op.rse.gate); break;
     case OP_RSE_APPLY: f(op.rsa.y); f(op.rsa.sc); f(op.rsa.gate); f(op.rsa.out); break;
     case OP_GCONV: f(op.gc.in); f(op.gc.out); break;
+    case OP_DCONV: f(op.dc.in); f(op.dc.off); f(op.dc.out); break;
     case OP_FUSE: for (auto& p : op.fuse.in) f(p); f(op.fuse.out); break;
     case OP_EFF_POST: for (auto& p : m->eff_post.cls) f(p); for (auto& p : m->eff_post.box) f(p); break;
     case OP_CMEAN: case OP_CSCALE: case OP_SE_GATE: case OP_SE_GATE_MEAN: case OP_WSCALE: case OP_POOL: case OP_SUB2: break;

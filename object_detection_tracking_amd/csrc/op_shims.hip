@@ -1017,6 +1017,37 @@ int odt_op_group_conv(int device, const float* x, int B, int H, int W, int C, co
   return get_dev(out, dout, nout);
 }
 
+int odt_op_deform_conv(int device, const float* x, int B, int H, int W, int C, const float* w_off, const float* b_off, const float* w,
+                       float* out, float* out_amax, float* offsets_out) {
+  return odt_op_deform_conv_view(device, x, B, H, W, C, H, W, C, w_off, b_off, w, out, out_amax, offsets_out);
+}
+
+int odt_op_deform_conv_view(int device, const float* x, int B, int Ha, int Wa, int ldc, int H, int W, int C, const float* w_off,
+                            const float* b_off, const float* w, float* out, float* out_amax, float* offsets_out) {
+  ODT_CHECK(x && w_off && b_off && w && out && out_amax && offsets_out, "odt_op_deform_conv: null argument");
+  ODT_CHECK(B >= 1 && H >= 1 && W >= 1 && Ha >= H && Wa >= W && ldc >= C && ldc % 4 == 0, "odt_op_deform_conv: bad sizes");
+  ODT_CHECK(C == 128 || C == 256 || C == 512, "odt_op_deform_conv: C must be 128, 256 or 512");
+  if (set_dev(device)) return 1;
+  std::vector<float> io(deform_offset_weight_elems(C)), iw(deform_weight_elems(C));
+  if (deform_pack_offset_weights(w_off, C, io.data()) || deform_pack_weights(w, C, iw.data())) return 1;
+  GBufs g;
+  DeformConvParams p; std::memset(&p, 0, sizeof(p));
+  const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  const size_t nin = (size_t)B * Ha * Wa * ldc, npx = (size_t)B * Ho * Wo;
+  float *dx, *dwo, *dbo, *dw, *doff, *dout;
+  unsigned* slot;
+  if (g.alloc("x", nin, &dx, -1, x) || g.alloc("w_off", io.size(), &dwo, -1, io.data()) || g.alloc("b_off", (size_t)18, &dbo, -1, b_off) ||
+      g.alloc("w", iw.size(), &dw, -1, iw.data()) || g.alloc("offsets", npx * 18, &doff) || g.alloc("out", npx * C, &dout) ||
+      g.alloc("range slot", (size_t)kAmaxWays, &slot, 0)) return 1;
+  p.in = dx; p.wt_off = dwo; p.b_off = dbo; p.wt = dw; p.off = doff; p.out = dout; p.out_amax = slot;
+  p.B = B; p.H = H; p.W = W; p.Ha = Ha; p.Wa = Wa; p.ldc = ldc; p.C = C; p.Ho = Ho; p.Wo = Wo;
+  if (launch_deform_conv(p, nullptr)) return 1;
+  if (g.check("odt_op_deform_conv")) return 1;
+  if (rse_read_amax(slot, out_amax)) return 1;
+  if (get_dev(offsets_out, doff, npx * 18)) return 1;
+  return get_dev(out, dout, npx * C);
+}
+
 int odt_op_effdet_post(int device, int B, int ncls, const int32_t* npix, int ldc_cls, int ldc_box,
                        const float* const* cls, const float* const* box, const float* anchors, int k, int max_out,
                        float score_thresh, float iou_thresh, float image_scale, int32_t* cand_idx, float* cand_boxes,

@@ -138,6 +138,21 @@ int upload_group_conv(odt_model* m, const std::string& scope, int C, const float
   return upload_raw(m, img, wt_out) || upload_raw(m, bias, bias_out);
 }
 
+// A deformable stage entry's conv2_offset (W [3,3,C,18] + b [18]: a bias, no BN) and conv2 (W [3,3,C,C]: neither bias nor BN,
+// nn.py:474-485 -- nothing is folded), re-packed for the kernels (conv_deform.hip).
+int upload_deform_conv(odt_model* m, const std::string& pre, int C, const float** wt_off, const float** b_off, const float** wt) {
+  const HostTensor* Wo = find_w(m, pre + "/conv2_offset/W");
+  const HostTensor* bo = find_w(m, pre + "/conv2_offset/b");
+  const HostTensor* W = find_w(m, pre + "/conv2/W");
+  ODT_CHECK(Wo != nullptr && bo != nullptr, "missing weight " + pre + "/conv2_offset/{W,b} (a deformable block: odt_config.use_deformable)");
+  ODT_CHECK(W != nullptr, "missing weight " + pre + "/conv2/W");
+  ODT_CHECK(Wo->data.size() == (size_t)9 * C * 18 && bo->data.size() == 18, "bad shape for " + pre + "/conv2_offset (W [3,3,C,18], b [18])");
+  ODT_CHECK(W->data.size() == (size_t)9 * C * C, "bad shape for " + pre + "/conv2/W");
+  std::vector<float> io(deform_offset_weight_elems(C)), iw(deform_weight_elems(C));
+  if (deform_pack_offset_weights(Wo->data.data(), C, io.data()) || deform_pack_weights(W->data.data(), C, iw.data())) return 1;
+  return upload_raw(m, io, wt_off) || upload_raw(m, bo->data, b_off) || upload_raw(m, iw, wt);
+}
+
 // The SE gate of bottleneck `pre` (reference nn.py:506-517) with conv3 + BN folded into fc1.  conv3 is 1x1 and BN affine, so
 // mean_HW(BN(conv3(t2))) = BN(conv3(mean_HW(t2))):
 //   w1[j][i] = sum_o conv3/W[i][o] * bnscale[o] * fc1/W[o][j]      b1[j] = sum_o bnshift[o] * fc1/W[o][j] + fc1/b[j]
@@ -327,6 +342,18 @@ int attach_split_weights(odt_model* m) {
       slot_of[op.gc.out] = slot;
       m->ops[oi].gc.out_amax = m->amax_dev + (size_t)slot * kAmaxWays;
       m->range_slot_name[slot] = "grouped conv2 output";
+      continue;
+    }
+    if (op.kind == OP_DCONV) {
+      // the deformable conv's output, likewise (the 18 offset channels feed that kernel alone: no slot)
+      slot_of.erase(op.dc.out); slot_of.erase(op.dc.off);
+      if (pol.family != 2) continue;
+      const int g = tail ? 1 : 0;
+      ODT_CHECK(m->amax_used[g] < odt_model::kAmaxSlots, "too many conv outputs for the range slots");
+      const int slot = (tail ? odt_model::kAmaxSlots : 0) + m->amax_used[g]++;
+      slot_of[op.dc.out] = slot;
+      m->ops[oi].dc.out_amax = m->amax_dev + (size_t)slot * kAmaxWays;
+      m->range_slot_name[slot] = "deformable conv2 output";
       continue;
     }
     if (op.kind == OP_POOL || op.kind == OP_SUB2) {

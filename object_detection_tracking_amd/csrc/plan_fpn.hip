@@ -63,6 +63,8 @@ int build_plan(odt_model* m) {
   int cin = 64;
   ODT_CHECK(cfg.block_kind >= 0 && cfg.block_kind <= 2, "odt_config.block_kind must be 0 (bottleneck), 1 (basic) or 2 (ResNeXt-32x4d)");
   ODT_CHECK(cfg.block_kind == 0 || !cfg.use_se, "squeeze-excitation is built for the plain bottleneck only (block_kind 0)");
+  ODT_CHECK(!cfg.use_deformable || (cfg.block_kind == 0 && !cfg.use_se),
+            "use_deformable is built for the plain bottleneck only (block_kind 0, no squeeze-excitation)");
   // conv2d's default padding (nn.py:337-381), TensorFlow's 'SAME': out = ceil(in / s), the smaller half of the padding in
   // front.  The rest lies behind the input, where the kernels read zeros anyway
   auto same_pad = [](int in, int s, int keff, int* out, int* before) {
@@ -155,9 +157,31 @@ int build_plan(odt_model* m) {
       if (upload_conv(m, pre + "/conv1", 1, 1, cin, ch, true, &wt, &bias)) return 1;
       if (add_conv(m, pre + "/conv1", x, cin, wt, bias, 1, 1, ch, 1, 1, 0, 0, x.h, x.w, 0, 0, nullptr, 0,
                    true, ch, &t1, "")) return 1;
-      if (upload_conv(m, pre + "/conv2", 3, 3, ch, ch, true, &wt, &bias)) return 1;
+      // --use_deformable (nn.py:469-485, 574-585): the stride-2 bottleneck that opens a stage, where block 0 is among the
+      // group's last three blocks
+      const bool deform = cfg.use_deformable != 0 && stride == 2 && cnt <= 3;
       int Ho, Wo;
-      if (stride == 2) {
+      if (deform) {
+        // conv2_offset (3x3, C -> 18, bias) + the deformable conv2 (no bias, BN or ReLU): conv_deform.hip.  With dilation 2 the
+        // reference pads this block's conv2 output once more (nn.py:493-497), ceil(h / 2) + 1 against the shortcut's h / 2: its
+        // graph does not build
+        ODT_CHECK(dil == 1, "use_deformable with use_dilations: the reference graph does not build (" + pre +
+                  " would be deformable and dilated); set use_dilations = 0");
+        ODT_CHECK(ch == 128 || ch == 256 || ch == 512, "deformable conv: C must be 128, 256 or 512 (" + pre + ")");
+        Ho = (x.h + 1) / 2; Wo = (x.w + 1) / 2;
+        Tensor toff{};
+        if (make_tensor(m, pre + "/conv2_offset", B, Ho, Wo, 18, &toff)) return 1;
+        if (make_tensor(m, pre + "/conv2", B, Ho, Wo, ch, &t2)) return 1;
+        Op od; od.kind = OP_DCONV;
+        DeformConvParams& dp = od.dc;
+        if (upload_deform_conv(m, pre, ch, &dp.wt_off, &dp.b_off, &dp.wt)) return 1;
+        dp.in = t1.d; dp.off = toff.d; dp.out = t2.d; dp.out_amax = nullptr;
+        dp.B = B; dp.H = t1.h; dp.W = t1.w; dp.Ha = t1.H; dp.Wa = t1.W; dp.ldc = t1.C; dp.C = ch; dp.Ho = Ho; dp.Wo = Wo;
+        od.dconv = m->dconv_ops++;
+        m->ops.push_back(od);
+      } else if (upload_conv(m, pre + "/conv2", 3, 3, ch, ch, true, &wt, &bias)) {
+        return 1;
+      } else if (stride == 2) {
         const int keff = 2 * dil + 1;
         const int h2 = (x.h + 1 - keff) / 2 + 1, w2 = (x.w + 1 - keff) / 2 + 1;
         const int off = dil != 1 ? 1 : 0;       // nn.py:493-497 second pad, after BN+ReLU

@@ -138,6 +138,11 @@ static int run_ops(odt_model* m, const void* src, int dtype, hipStream_t st, siz
         if (launch_group_conv(op.gc, st)) return 1;
         if (m->profile) ODT_HIP(hipEventRecord(m->ev_gconv[2 * op.gconv + 1], st));
         break;
+      case OP_DCONV:              // --use_deformable stage entry: conv2_offset, then the deformable conv2
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_dconv[3 * op.dconv], st));
+        if (launch_deform_conv(op.dc, st, m->profile ? m->ev_dconv[3 * op.dconv + 1] : nullptr)) return 1;
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_dconv[3 * op.dconv + 2], st));
+        break;
       case OP_MASK_SELECT:
         if (launch_mask_select(m->mask_sel, st)) return 1;
         break;
@@ -208,6 +213,12 @@ static int finish_profile(odt_model* m, hipStream_t st) {
     ODT_HIP(hipEventElapsedTime(&t, m->ev_gconv[2 * i], m->ev_gconv[2 * i + 1]));
     m->prof_gconv_ms += t;
   }
+  for (int i = 0; i < m->dconv_ops; ++i) {
+    float t0 = 0, t1 = 0;
+    ODT_HIP(hipEventElapsedTime(&t0, m->ev_dconv[3 * i], m->ev_dconv[3 * i + 1]));
+    ODT_HIP(hipEventElapsedTime(&t1, m->ev_dconv[3 * i + 1], m->ev_dconv[3 * i + 2]));
+    m->prof_doff_ms += t0; m->prof_dconv_ms += t1;
+  }
   ++m->prof_forwards;
   float tt = 0;
   ODT_HIP(hipEventElapsedTime(&tt, m->ev_total[0], m->ev_total[1]));
@@ -254,6 +265,7 @@ int run_plan(odt_model* m, const void* frames, int dtype, int on_device, hipStre
   if (m->profile) {
     while (m->ev.size() < 2 * m->convs.size()) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev.push_back(e); }
     while (m->ev_gconv.size() < 2 * (size_t)m->gconv_ops) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_gconv.push_back(e); }
+    while (m->ev_dconv.size() < 3 * (size_t)m->dconv_ops) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_dconv.push_back(e); }
     for (int i = 0; i < 2; ++i) if (!m->ev_total[i]) ODT_HIP(hipEventCreate(&m->ev_total[i]));
     ODT_HIP(hipEventRecord(m->ev_total[0], st));
   }
@@ -341,6 +353,7 @@ int odt_destroy(odt_handle h) {
   (void)hipDeviceSynchronize();
   for (auto e : h->ev) (void)hipEventDestroy(e);
   for (auto e : h->ev_gconv) (void)hipEventDestroy(e);
+  for (auto e : h->ev_dconv) (void)hipEventDestroy(e);
   for (auto e : h->ev_total) if (e) (void)hipEventDestroy(e);
   for (auto& sl : h->slot) {
     if (sl.pin_in) (void)hipHostFree(sl.pin_in);
@@ -693,6 +706,7 @@ int odt_profile_enable(odt_handle h, int enable) {
   h->profile = enable != 0;
   h->prof_conv_ms = h->prof_conv_flops = h->prof_total_ms = 0; h->prof_launches = 0;
   h->prof_gconv_ms = 0; h->prof_forwards = 0;
+  h->prof_doff_ms = h->prof_dconv_ms = 0;
   h->prof_layer_ms.assign(h->convs.size(), 0.0);
   return 0;
 }
@@ -759,7 +773,8 @@ int odt_describe(odt_handle h, char* buf, int cap) {
                 "\"memory\": {\"device_bytes\": %zu, \"activation_arena_bytes\": [%zu, %zu], \"arena_tensors\": %zu, "
                 "\"arena_tensor_bytes_unshared\": %zu, \"dedicated_tensor_bytes\": %zu, \"keep_taps\": %d}, \"convs_cut_into_batch_ranges\": %d, "
                 "\"use_se\": %d, \"se_blocks\": %d, \"se_blocks_conv1_on_fp16x2\": %d, \"block_kind\": \"%s\", \"group_conv_launches\": %d, "
-                "\"group_conv_profiled_ms\": %.6f, \"profiled_forwards\": %d}",
+                "\"group_conv_profiled_ms\": %.6f, \"profiled_forwards\": %d, \"use_deformable\": %d, \"deform_conv_launches\": %d, "
+                "\"deform_offset_profiled_ms\": %.6f, \"deform_conv_profiled_ms\": %.6f}",
                 h->policy.arith != 0 && fam[2] > 0 ? "f32 through fp16x2 / bf16x3 split products"
                     : (h->policy.arith != 0 && fam[1] + fam[3] > 0 ? "f32 through bf16x3 split products" : "exact f32 MFMA"),
                 (int)h->convs.size() - nfused, nfused, fam[0], fam[1] + fam[3], fam[2], h->convs_h2f, h->blocks_fused, h->stem_fused, h->mb_fused, fam[3], fam[1], fam[2], nsk, h->policy.family,
@@ -767,7 +782,7 @@ int odt_describe(odt_handle h, char* buf, int cap) {
                 dev_bytes, h->arena_bytes[0], h->arena_bytes[1], h->vt.size(), h->virtual_tensor_bytes,
                 h->dedicated_tensor_bytes, h->cfg.keep_taps, h->chunked_convs, h->cfg.use_se != 0 ? 1 : 0, h->se_blocks, se_conv1_h2,
                 h->cfg.block_kind == 1 ? "basic" : (h->cfg.block_kind == 2 ? "resnext32x4d" : "bottleneck"), h->gconv_ops,
-                h->prof_gconv_ms, h->prof_forwards);
+                h->prof_gconv_ms, h->prof_forwards, h->cfg.use_deformable != 0 ? 1 : 0, h->dconv_ops, h->prof_doff_ms, h->prof_dconv_ms);
   ODT_CHECK((int)std::strlen(tmp) < cap, "odt_describe: buffer too small");
   std::strncpy(buf, tmp, cap - 1); buf[cap - 1] = 0;
   return 0;

@@ -33,7 +33,7 @@ from .nn import get_new_hw
 from .range_guard import RangeGuard
 from .frozen_pb import load_frozen_pb
 from .tf_checkpoint import load_checkpoint
-from .weights import backbone_block_kind, expand_class_agnostic_box, load_npz, select_partial_classes
+from .weights import backbone_block_kind, deformable_groups, expand_class_agnostic_box, load_npz, select_partial_classes
 
 
 class TensorHandle(object):
@@ -133,6 +133,7 @@ class _Engine(object):
     c.tail_overlap = -1 if getattr(config, "tail_overlap", True) in (False, -1) else 0      # (False: everything on the compute stream)
     c.use_se = int(bool(getattr(config, "use_se", False)))      # model version 6: squeeze-excitation in every bottleneck
     c.block_kind = backbone_block_kind(config)                  # include/odt.h: 0 bottleneck | 1 basic | 2 ResNeXt-32x4d
+    c.use_deformable = int(bool(getattr(config, "use_deformable", False)))      # deformable conv2 in the stage-entry bottlenecks
     B, P, Cn = batch, self.per_im, self.channels
     self._boxes = np.zeros((B, P, 4), np.float32)
     self._probs = np.zeros((B, P), np.float32)
@@ -388,7 +389,7 @@ class _DetectorBase(object):
         raise ValueError("weights: pass a {name: array} dict or set config.model_path to a "
                          "Tensorpack-style .npz (reference obj_detect_tracking.py:417-435), a "
                          "TF checkpoint directory / prefix, or a frozen .pb (--is_load_from_pb)")
-    unsupported = [f for f in ("use_gn", "use_deformable", "add_relation_nn",
+    unsupported = [f for f in ("use_gn", "add_relation_nn",
                                "use_conv_frcnn_head", "use_att_frcnn_head",
                                "use_small_object_head", "use_cascade_rcnn")
                    if getattr(self.config, f, False)]
@@ -401,6 +402,24 @@ class _DetectorBase(object):
       if getattr(self.config, f, False) and getattr(self.config, "use_se", False):
         raise NotImplementedError("graph variants not built on this path: %s together with use_se (the reference builds "
                                   "these blocks without squeeze-excitation and says nothing)" % f)
+    if getattr(self.config, "use_deformable", False):
+      # --use_deformable (nn.py:469-485, 574-585): a deformable conv2 in the stride-2 bottleneck that opens a stage
+      for f in ("use_resnext", "use_basic_block"):
+        if getattr(self.config, f, False):
+          raise NotImplementedError("graph variants not built on this path: use_deformable together with %s (the reference "
+                                    "takes the flag for these blocks, ignores it and says nothing)" % f)
+      if getattr(self.config, "use_se", False):
+        raise NotImplementedError("graph variants not built on this path: use_deformable together with use_se")
+      groups = deformable_groups(self.config)
+      if 3 in groups and getattr(self.config, "use_dilations", False):
+        raise ValueError("use_deformable with use_dilations: the reference pads the deformable, dilated group3/block0 once more "
+                         "(nn.py:493-497) and its graph does not build (ceil(h / 2) + 1 rows against the shortcut's h / 2); "
+                         "pass use_dilations=False (or version=2) with use_deformable=True")
+      missing = [n for g in groups for n in ("group%d/block0/conv2_offset/W" % g, "group%d/block0/conv2_offset/b" % g)
+                 if n not in weights]
+      if missing:
+        raise NotImplementedError("a deformable graph cannot be built from weights without conv2_offset variables: missing "
+                                  + ", ".join(missing[:4]) + (" ... (%d in all)" % len(missing) if len(missing) > 4 else ""))
     if getattr(self.config, "use_se", False):
       # version 6 (nn.py:506-517): every bottleneck carries fc1 / fc2.  Checked here, not at the first frame: a plan cannot be
       # built without them, and a model that cannot run should not construct
@@ -634,7 +653,8 @@ def config_from_weights(weights, add_mask=False, is_multi=False, **overrides):
   bottlenecks per stage, classes, FPN / head widths, class-agnostic box head.  Everything that is a graph constant
   rather than a tensor (rpn_test_post_nms_topk, thresholds, frame size) keeps the reference's defaults unless
   overridden.  ``group0/block0/fc1/W`` present means a squeeze-excitation backbone (use_se); unless overridden,
-  use_dilations=False follows from it: the only published SE model (version 6) is undilated.  No ``group0/block0/conv3/W``
+  use_dilations=False follows from it: the only published SE model (version 6) is undilated.  A
+  ``groupG/block0/conv2_offset/W`` means deformable stage entries (use_deformable, and no dilations).  No ``group0/block0/conv3/W``
   means basic blocks (use_basic_block); a ``conv2/W`` of [3,3,C/32,C] means ResNeXt-32x4d (use_resnext)."""
   from .config import make_config
   blocks = [0, 0, 0, 0]
@@ -650,6 +670,8 @@ def config_from_weights(weights, add_mask=False, is_multi=False, **overrides):
             im_batch_size=2 if is_multi else 1)
   if "group0/block0/fc1/W" in weights:
     kw.update(use_se=True, use_dilations=False)
+  if any(k.endswith("/block0/conv2_offset/W") for k in weights):
+    kw.update(use_deformable=True, use_dilations=False)      # (the reference graph does not build with both)
   if "group0/block0/conv3/W" not in weights:
     kw.update(use_basic_block=True)            # resnet_basicblock: two 3x3 convs, no conv3
   else:

@@ -490,6 +490,28 @@ def group_conv(x, w, bias, stride=1, dil=1, pad=None, out_hw=None, relu=True, li
   return out, float(amax[0])
 
 
+def deform_conv(x, w_off, b_off, w, lib=None, device=0, view=None):
+  """The deformable conv2 of a --use_deformable stage entry (csrc/conv_deform.hip; reference nn.py:469-485, 1642-1712): x
+  [B,H,W,C], C in {128, 256, 512}; w_off [3,3,C,18] + b_off [18] give the offsets at the even positions (a 3x3 stride-2 conv
+  with one zero row / column in front; channel 2 n the row offset, 2 n + 1 the column offset of tap n = 3 ky + kx); w
+  [3,3,C,C] multiplies the nine bilinear samples at the clamped coordinates.  Returns (out [B,ceil(H/2),ceil(W/2),C], recorded
+  |max| of out, offsets [B,ceil(H/2),ceil(W/2),18]).  With view = (H, W, C), x is an allocation [B,Ha,Wa,ldc] of which the op reads
+  rows < H, columns < W and channels < C, as the plan reads a pitched tensor."""
+  lib = _L(lib)
+  x = f32(x); w_off = f32(w_off); b_off = f32(b_off); w = f32(w)
+  B, Ha, Wa, ldc = x.shape
+  H, W, C = (Ha, Wa, ldc) if view is None else view
+  assert w_off.shape == (3, 3, C, 18) and b_off.shape == (18,) and w.shape == (3, 3, C, C)
+  Ho, Wo = (H + 1) // 2, (W + 1) // 2
+  out = np.empty((B, Ho, Wo, C), np.float32); off = np.empty((B, Ho, Wo, 18), np.float32); amax = np.zeros(1, np.float32)
+  if view is None:
+    lib.check(lib.dll.odt_op_deform_conv(device, fptr(x), B, H, W, C, fptr(w_off), fptr(b_off), fptr(w), fptr(out), fptr(amax), fptr(off)))
+  else:
+    lib.check(lib.dll.odt_op_deform_conv_view(device, fptr(x), B, Ha, Wa, ldc, H, W, C, fptr(w_off), fptr(b_off), fptr(w), fptr(out),
+                                              fptr(amax), fptr(off)))
+  return out, float(amax[0]), off
+
+
 def se_tail(t2, w3, b3, fc1, fc2, shortcut, lib=None, device=0):
   """The tail of an SE bottleneck (reference nn.py:502-521) as the plan runs it: pool of t2 [B,H,W,ch] -> gate (conv3 + BN
   folded into fc1 = (W [4 ch, ch / 4], b), fc2 = (W [ch / 4, 4 ch], b)) -> conv3 (w3 [ch, 4 ch] with BN folded, + b3) ->

@@ -34,12 +34,22 @@ def backbone_block_kind(config):
   return 1 if getattr(config, "use_basic_block", False) else 0
 
 
+def deformable_groups(config):
+  """The groups whose block 0 is deformable under --use_deformable (reference nn.py:469-485, 574-585): a resnet_bottleneck of
+  stride 2 (block 0 of group 1, 2 or 3) that is among the last three blocks of its group.  [3, 4, 23, 3] -> [3]."""
+  if not getattr(config, "use_deformable", False) or backbone_block_kind(config) != 0:
+    return []
+  return [g for g in (1, 2, 3) if 1 <= config.resnet_num_block[g] <= 3]
+
+
 def backbone_conv_specs(config):
   """Yield (scope, kh, cin, cout, has_bn, has_bias) for every conv on the path,
   in execution order (reference nn.py:843-1014, models.py:979-1009); cin is W's third dimension -- the channels per
-  group of a grouped conv."""
+  group of a grouped conv.  A deformable block's conv2 has neither BN nor bias; its conv2_offset is not listed here
+  (synthetic_weights draws it from a generator of its own)."""
   blocks = config.resnet_num_block
   kind = backbone_block_kind(config)
+  deform = deformable_groups(config)
   yield ("conv0", 7, 3, 64, True, False)
   cin = 64
   for g, (feat, cnt) in enumerate(zip((64, 128, 256, 512), blocks)):
@@ -58,7 +68,7 @@ def backbone_conv_specs(config):
         yield (pre + "/conv3", 1, feat * 2, feat * 4, True, False)
       else:
         yield (pre + "/conv1", 1, cin, feat, True, False)
-        yield (pre + "/conv2", 3, feat, feat, True, False)
+        yield (pre + "/conv2", 3, feat, feat, not (i == 0 and g in deform), False)
         yield (pre + "/conv3", 1, feat, feat * 4, True, False)
       if i == 0:
         yield (pre + "/convshortcut", 1, cin, feat * 4, True, False)
@@ -87,6 +97,9 @@ def synthetic_weights(config, seed=0):
   rng = np.random.default_rng(seed)
   w = {}
   basic = backbone_block_kind(config) == 1
+  # a deformable block's conv2 has no BN (nn.py:483-485): its four draws are made and dropped, so that every other variable
+  # stays bit-identical to the weights of the same seed without the flag
+  bn_less = {"group%d/block0/conv2" % g for g in deformable_groups(config)}
 
   def normal(shape, std):
     return (rng.standard_normal(shape, dtype=np.float32) * np.float32(std))
@@ -106,15 +119,18 @@ def synthetic_weights(config, seed=0):
       if scope == "rpn/class":
         b = b + np.float32(1.0)
       w[scope + "/b"] = b
-    if has_bn:
+    if has_bn or scope in bn_less:
+      bn = {}
       gamma = rng.uniform(0.9, 1.1, cout).astype(np.float32)
       if scope.endswith("/conv3") or (basic and scope.endswith("/conv2")):      # the block's last BN
         gamma *= np.float32(0.12)
-      w[scope + "/bn/gamma"] = gamma
-      w[scope + "/bn/beta"] = normal((cout,), 0.02)
-      w[scope + "/bn/mean/EMA"] = normal((cout,), 0.05)
-      w[scope + "/bn/variance/EMA"] = rng.uniform(0.8, 1.2, cout).astype(
+      bn[scope + "/bn/gamma"] = gamma
+      bn[scope + "/bn/beta"] = normal((cout,), 0.02)
+      bn[scope + "/bn/mean/EMA"] = normal((cout,), 0.05)
+      bn[scope + "/bn/variance/EMA"] = rng.uniform(0.8, 1.2, cout).astype(
           np.float32)
+      if has_bn:
+        w.update(bn)
   dim = config.fpn_frcnn_fc_head_dim
   ch = config.fpn_num_channel
   nc = config.num_class
@@ -154,6 +170,16 @@ def synthetic_weights(config, seed=0):
         w[pre + "/fc1/b"] = se_normal((r,), 0.02)
         w[pre + "/fc2/W"] = se_normal((r, C), np.sqrt(2.0 / r))
         w[pre + "/fc2/b"] = se_normal((C,), 0.5)
+  if deformable_groups(config):
+    # --use_deformable (nn.py:469-485): conv2_offset of the deformable stage entries from a generator of its own.  Offsets of
+    # a pixel or two (std 1.3 - 1.5 px, |max| 3.5 - 5 px on the synthetic frames): nearly every sample coordinate is fractional
+    # and a good part of them clamps at the border of the small test maps
+    d_rng = np.random.default_rng([seed, 7])
+    for g in deformable_groups(config):
+      C = (64, 128, 256, 512)[g]
+      pre = "group%d/block0/conv2_offset" % g
+      w[pre + "/W"] = d_rng.standard_normal((3, 3, C, 18), dtype=np.float32) * np.float32(1.5 * np.sqrt(1.0 / (9 * C)))
+      w[pre + "/b"] = d_rng.standard_normal((18,), dtype=np.float32) * np.float32(0.5)
   return w
 
 

@@ -1,13 +1,18 @@
 #!/usr/bin/env python
 """The detector step of the backbones the plan can build, on one MI355X: ResNet-101 (the default), ResNeXt-101 32x4d
-(--use_resnext, [3,4,23,3]), ResNet-18 and ResNet-34 (--resnet18 / --resnet34).
+(--use_resnext, [3,4,23,3]), ResNet-18 and ResNet-34 (--resnet18 / --resnet34), and ResNet-101 without dilations plain and with
+--use_deformable (a deformable group3/block0; the reference graph does not build with dilations).
 
 python tools/bench_backbones.py [--batch 8] [--height 1080] [--width 1920] [--topk 300] [--steps 10] [--warmup 2]
   One child process per backbone (a fresh runtime each; nothing of one handle is resident under the next).  Multi graph,
   --rotate resident uint8 batches taken in turn, device-synchronised timing after a warm-up (as bench.py).  Synthetic
   weights of seed 0.  For ResNeXt a second, profiled pass times every launch of the 32-group 3x3 conv (csrc/conv_group.hip)
   and prints the mean next to two floors computed here from the shapes: the bytes of its two tensors over the project's
-  measured copy rate, and its f32 products over the measured rate of the exact-f32 MFMA.
+  measured copy rate, and its f32 products over the measured rate of the exact-f32 MFMA.  For the deformable R101 a profiled
+  pass times conv2_offset and the deformable conv (csrc/conv_deform.hip) next to the latter's product floor.
+  Without --backbones the four block kinds run (r101, resnext101, resnet34, resnet18), as before the deformable rows.
+python tools/bench_backbones.py --backbones r101_nodil,r101_deformable
+  Only these, in this order, in one run: profiles/backbones_deformable_b8_1080p.txt.
 python tools/bench_backbones.py --only resnext101 --steps 3
   Just that handle in this process: the program to put behind `rocprofv3 --kernel-trace --stats --` for per-kernel times.
 One JSON line per backbone, and one with all of them at the end."""
@@ -17,7 +22,9 @@ import numpy as np
 
 COPY_RATE = 6.29e12      # bytes/s, the project's measured device copy rate
 F32_MFMA_RATE = 155e12   # FLOP/s, v_mfma_f32_16x16x4_f32 back to back on every SIMD
-BACKBONES = {"r101": {}, "resnext101": dict(use_resnext=True), "resnet34": dict(resnet34=True), "resnet18": dict(resnet18=True)}
+BACKBONES = {"r101": {}, "resnext101": dict(use_resnext=True), "resnet34": dict(resnet34=True), "resnet18": dict(resnet18=True),
+             "r101_nodil": dict(use_dilations=False), "r101_deformable": dict(use_dilations=False, use_deformable=True)}
+DEFAULT = ("r101", "resnext101", "resnet34", "resnet18")   # what a run without --backbones measures (profiles/backbones_b8_1080p.txt)
 
 
 def group_conv_shapes(cfg, B, H, W):
@@ -32,6 +39,19 @@ def group_conv_shapes(cfg, B, H, W):
       ho, wo = -(-h // stride), -(-w // stride)
       out.append((2 * ch, h, w, ho, wo, stride, dil))
       h, w = ho, wo
+  return out
+
+
+def deform_conv_shapes(cfg, H, W):
+  """[(C, Ho, Wo)] of the plan's deformable convs, by the plan's rules: the stride-2 bottleneck that opens group 1-3 where
+  the group has at most three blocks; C is the block's conv2 width, Ho x Wo its output map."""
+  h, w = -(-H // 32) * 32 // 4, -(-W // 32) * 32 // 4
+  out = []
+  for g, (ch, cnt) in enumerate(zip((64, 128, 256, 512), cfg.resnet_num_block)):
+    if g > 0:
+      h, w = -(-h // 2), -(-w // 2)
+      if cfg.use_deformable and cnt <= 3:
+        out.append((ch, h, w))
   return out
 
 
@@ -82,6 +102,19 @@ def child(a, name):
     per_fwd = dp["group_conv_profiled_ms"] / max(1, dp["profiled_forwards"])
     res["group_conv"] = {"ms_per_step": per_fwd, "ms_per_launch": per_fwd / len(shapes), "bytes_per_step": by, "flop_per_step": fl,
                          "floor_ms_bytes_over_copy_rate": by / COPY_RATE * 1e3, "floor_ms_flop_over_f32_mfma_rate": fl / F32_MFMA_RATE * 1e3}
+  if d.get("deform_conv_launches", 0) > 0:
+    e.profile(True)
+    run(a.steps)
+    dp = e.describe()
+    e.profile(False)
+    shapes = deform_conv_shapes(cfg, H, W)      # R50 / R101 / R152: group3/block0 alone, C = 512 on the 1/32 map
+    assert len(shapes) == d["deform_conv_launches"], (len(shapes), d["deform_conv_launches"])
+    px = sum(B * ho * wo for _, ho, wo in shapes)
+    fl = sum(2.0 * B * ho * wo * 9 * C * C for C, ho, wo in shapes)
+    n = max(1, dp["profiled_forwards"])
+    res["deform_conv"] = {"offset_ms_per_step": dp["deform_offset_profiled_ms"] / n, "conv_ms_per_step": dp["deform_conv_profiled_ms"] / n,
+                          "output_pixels": px, "flop_per_step": fl, "offset_flop_per_step": sum(2.0 * B * ho * wo * 9 * C * 18 for C, ho, wo in shapes),
+                          "floor_ms_flop_over_f32_mfma_rate": fl / F32_MFMA_RATE * 1e3}
   m.close()
   print(json.dumps(res), flush=True)
   return res
@@ -98,13 +131,17 @@ def main():
   ap.add_argument("--rounds", type=int, default=3)
   ap.add_argument("--rotate", type=int, default=4)
   ap.add_argument("--only", default="", choices=[""] + sorted(BACKBONES))
+  ap.add_argument("--backbones", default="", help="comma-separated subset of %s (default: %s)" % (", ".join(BACKBONES), ",".join(DEFAULT)))
   ap.add_argument("--device", type=int, default=0)
   a = ap.parse_args()
   if a.only:
     child(a, a.only)
     return
   out = {}
-  for name in BACKBONES:
+  names = [n for n in a.backbones.split(",") if n] or list(DEFAULT)
+  for name in names:
+    if name not in BACKBONES:
+      sys.exit("unknown backbone %s" % name)
     cmd = [sys.executable, os.path.abspath(__file__), "--only", name] + \
         [x for k in ("batch", "height", "width", "topk", "steps", "warmup", "rounds", "rotate", "device") for x in ("--" + k, str(getattr(a, k)))]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
@@ -121,6 +158,11 @@ def main():
             "%.2f TB/s, %.0f GFLOP -> %.3f ms at %.0f TF" % (res["group_conv_launches"], g["ms_per_step"], g["ms_per_launch"],
             g["bytes_per_step"] / 1e9, g["floor_ms_bytes_over_copy_rate"], COPY_RATE / 1e12, g["flop_per_step"] / 1e9,
             g["floor_ms_flop_over_f32_mfma_rate"], F32_MFMA_RATE / 1e12))
+    if "deform_conv" in res:
+      g = res["deform_conv"]
+      print("            deformable conv2: %.3f ms/step measured (+ conv2_offset %.3f ms);  floor from the shape: %.1f GFLOP -> %.3f ms "
+            "at %.0f TF" % (g["conv_ms_per_step"], g["offset_ms_per_step"], g["flop_per_step"] / 1e9, g["floor_ms_flop_over_f32_mfma_rate"],
+            F32_MFMA_RATE / 1e12))
   print(json.dumps(out), flush=True)
 
 
