@@ -436,6 +436,26 @@ int odt_op_roi_align(int device, int B, int C, const int* hs, const int* ws,
                      const float* const* feats, const float* strides,
                      const float* boxes, const int32_t* box_ind, int R,
                      float* out_nchw, float* pooled);
+/* The same kernel with the parameters the plans give it (one launch_roi_align): L = 1..5 levels, dims [L][5] = h, w,
+ * alloc_h, alloc_w, ldc per level, feats[l] the whole allocation [B,alloc_h,alloc_w,ldc] of which the kernel reads the
+ * view [:h,:w,:C] (ldc % 4 == 0); boxes [B * per_image,4], box r belongs to image r / per_image; count [B] valid rows
+ * per image or NULL (all); levels [B * per_image] in level0 .. level0 + L - 1 or NULL (FPN area rule, L >= 4);
+ * out_size 7 (0) or 14; pack_rows 1: output rows packed over the valid rows in image order, 0: row r stays row r;
+ * want_amax: record the |max| of out_nhwc (as float bits, from 0) into amax [1] and write rows past count[b] as zeros
+ * (pack_rows 0).  Outputs (each may be NULL) out_nhwc [R,o,o,C], out_nchw [R,C,o,o], pooled [R,C] (7 only): rows the
+ * kernel did not write read back as 0x7F7F7F7F; every device buffer ends in a guard region as for the ops below.
+ * A level one pixel high (wide) is defined: sample j of that axis lies at (y0 + sh / 2 - 0.5) + j * sh level pixels
+ * and counts only where that is exactly 0; every other sample is the extrapolation value 0. */
+int odt_op_roi_align_plan(int device, int B, int C, int L, const int32_t* dims, const float* const* feats,
+                          const float* strides, const float* boxes, int per_image, const int32_t* count,
+                          const int32_t* levels, int level0, int out_size, int pack_rows, int want_amax,
+                          float* out_nhwc, float* out_nchw, float* pooled, uint32_t* amax);
+/* mask head tail (launch_mask_select; models.py:951-962): logits [B * per_image,14,14,4,ld] -- the deconv's (dy,dx)
+ * sub-pixel channels major, class minor at the padded stride ld -- labels [B * per_image] 1-based, valid [B] rows per
+ * image -> masks [B * per_image,28,28] = sigmoid of the label's logit at pixel (y, x) <- cell (y / 2, x / 2), sub-pixel
+ * (y % 2) * 2 + x % 2; rows past valid[b] are zeros.  Guard regions as above. */
+int odt_op_mask_select(int device, const float* logits, int ld, const int32_t* labels, const int32_t* valid, int B,
+                       int per_image, float* masks);
 /* inference tail (models.py:828-843 + fastrcnn_predictions :1258-1304 or
  * fastrcnn_predictions_multibatch :2924-2976).  cls_logits [B*K,C],
  * box_logits [B*K,C,4] (class 0 present, ignored), props [B,K,4], nprops [B]. */

@@ -109,7 +109,7 @@ class OdtLib(object):
       "odt_profile_read", "odt_profile_layer", "odt_probe_mfma_bf16", "odt_nn_cosine", "odt_op_conv2d", "odt_op_conv2d_cat",
       "odt_op_bottleneck_tail", "odt_op_bottleneck_block", "odt_op_stem", "odt_op_conv_choice", "odt_op_last_conv", "odt_op_preprocess",
       "odt_op_maxpool", "odt_op_topk", "odt_op_nms", "odt_op_proposals",
-      "odt_op_roi_align", "odt_op_detections", "odt_op_class_nms",
+      "odt_op_roi_align", "odt_op_roi_align_plan", "odt_op_mask_select", "odt_op_detections", "odt_op_class_nms",
       "odt_op_dwconv", "odt_op_se_gate", "odt_op_rse_gate", "odt_op_rse_apply", "odt_op_se_tail", "odt_op_group_conv", "odt_op_deform_conv", "odt_op_deform_conv_view", "odt_op_bifpn_fuse", "odt_op_mbconv_expand_dw", "odt_op_effdet_post",
       "odt_op_preprocess_rgb", "odt_forward_serial", "odt_mask_rle", "odt_op_mask_rle", "odt_tracker_create", "odt_tracker_destroy",
       "odt_tracker_predict", "odt_tracker_update", "odt_tracker_tracks", "odt_lsap", "odt_tracker_nms",
@@ -176,6 +176,9 @@ class OdtLib(object):
     d.odt_op_roi_align.argtypes = [C.c_int, C.c_int, C.c_int, c_int_p, c_int_p,
                                    C.POINTER(c_float_p), c_float_p, c_float_p, c_int_p, C.c_int,
                                    c_float_p, c_float_p]
+    d.odt_op_roi_align_plan.argtypes = [C.c_int] * 4 + [c_int_p, C.POINTER(c_float_p), c_float_p, c_float_p, C.c_int, c_int_p,
+                                        c_int_p] + [C.c_int] * 4 + [c_float_p] * 3 + [C.POINTER(C.c_uint32)]
+    d.odt_op_mask_select.argtypes = [C.c_int, c_float_p, C.c_int, c_int_p, c_int_p, C.c_int, C.c_int, c_float_p]
     d.odt_tracker_create.argtypes = [C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(C.c_void_p)]
     d.odt_tracker_destroy.argtypes = [C.c_void_p]

@@ -499,6 +499,9 @@ int launch_nms(const float* boxes, const float* scores, int n, int max_out, floa
                int* idx_out, int* n_out, hipStream_t stream);
 
 // --------------------------------------------------------------- ROIAlign (K9,K14)
+// A level one pixel high (wide) is defined, where the reference divides by h - 1 = 0: on that axis sample j lies at
+// (y0 + sh / 2 - 0.5) + j * sh in level pixels (sh = box side / samples) and counts only where that is exactly 0 -- every
+// sample off the single row (column) is the extrapolation value 0, as on any other level.
 struct RoiAlignParams {
   const float* feat[5];  // NHWC [B,h,w,C] (sliced dims h,w ; pixel stride ldc); 5th level: EfficientDet P7
   int h[5], w[5], ldc[5], alloc_h[5], alloc_w[5];

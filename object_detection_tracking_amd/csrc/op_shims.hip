@@ -689,6 +689,75 @@ int odt_op_roi_align(int device, int B, int C, const int* hs, const int* ws, con
   return 0;
 }
 
+int odt_op_roi_align_plan(int device, int B, int C, int L, const int32_t* dims, const float* const* feats, const float* strides,
+                          const float* boxes, int per_image, const int32_t* count, const int32_t* levels, int level0,
+                          int out_size, int pack_rows, int want_amax, float* out_nhwc, float* out_nchw, float* pooled,
+                          uint32_t* amax) {
+  ODT_CHECK(dims && feats && strides && boxes, "odt_op_roi_align_plan: null argument");
+  ODT_CHECK(B >= 1 && per_image >= 1 && C >= 1 && L >= 1 && L <= 5, "odt_op_roi_align_plan: bad sizes");
+  ODT_CHECK(out_size == 0 || out_size == kRoiOut || out_size == 2 * kRoiOut, "odt_op_roi_align_plan: output side must be 7 or 14");
+  ODT_CHECK(levels != nullptr || L >= 4, "odt_op_roi_align_plan: the FPN level rule needs four levels");
+  const int R = B * per_image, OO = out_size == 2 * kRoiOut ? 4 * kRoiOut * kRoiOut : kRoiOut * kRoiOut;
+  for (int l = 0; l < L; ++l) {
+    const int32_t* d = dims + 5 * l;      // h, w, alloc_h, alloc_w, ldc
+    ODT_CHECK(feats[l] != nullptr && d[0] >= 1 && d[1] >= 1 && d[2] >= d[0] && d[3] >= d[1] && d[4] >= C && strides[l] > 0.f,
+              "odt_op_roi_align_plan: a level's view must lie inside its allocation");
+  }
+  for (int r = 0; levels != nullptr && r < R; ++r)
+    ODT_CHECK(levels[r] >= level0 && levels[r] < level0 + L, "odt_op_roi_align_plan: level out of range");
+  for (int b = 0; count != nullptr && b < B; ++b)
+    ODT_CHECK(count[b] >= 0 && count[b] <= per_image, "odt_op_roi_align_plan: count out of range");
+  if (set_dev(device)) return 1;
+  GBufs g;
+  RoiAlignParams p; std::memset(&p, 0, sizeof(p));
+  static const char* names[5] = {"feat0", "feat1", "feat2", "feat3", "feat4"};
+  for (int l = 0; l < L; ++l) {
+    const int32_t* d = dims + 5 * l;
+    float* df;
+    if (g.alloc(names[l], (size_t)B * d[2] * d[3] * d[4], &df, -1, feats[l])) return 1;
+    p.feat[l] = df; p.h[l] = d[0]; p.w[l] = d[1]; p.alloc_h[l] = d[2]; p.alloc_w[l] = d[3]; p.ldc[l] = d[4];
+    p.inv_stride[l] = (float)(1.0 / (double)strides[l]);
+  }
+  float* dbox; int *dcount = nullptr, *dlev = nullptr;
+  if (g.alloc("boxes", (size_t)R * 4, &dbox, -1, boxes)) return 1;
+  if (count != nullptr && g.alloc("count", (size_t)B, &dcount, -1, count)) return 1;
+  if (levels != nullptr && g.alloc("levels", (size_t)R, &dlev, -1, levels)) return 1;
+  if (out_nhwc != nullptr && g.alloc("out_nhwc", (size_t)R * OO * C, &p.out_nhwc)) return 1;
+  if (out_nchw != nullptr && g.alloc("out_nchw", (size_t)R * OO * C, &p.out_nchw)) return 1;
+  if (pooled != nullptr && g.alloc("pooled", (size_t)R * C, &p.pooled)) return 1;
+  if (want_amax && g.alloc("amax", (size_t)1, &p.amax, 0)) return 1;
+  p.levels = dlev; p.level0 = level0; p.C = C; p.boxes = dbox; p.box_ind = nullptr; p.per_image = per_image; p.count = dcount;
+  p.R_cap = R; p.out_size = out_size; p.pack_rows = pack_rows;
+  if (launch_roi_align(p, nullptr)) return 1;
+  if (g.check("odt_op_roi_align_plan")) return 1;
+  if (get_dev(out_nhwc, p.out_nhwc, (size_t)R * OO * C) || get_dev(out_nchw, p.out_nchw, (size_t)R * OO * C) ||
+      get_dev(pooled, p.pooled, (size_t)R * C)) return 1;
+  if (want_amax) return get_dev(amax, p.amax, (size_t)1);
+  return 0;
+}
+
+int odt_op_mask_select(int device, const float* logits, int ld, const int32_t* labels, const int32_t* valid, int B,
+                       int per_image, float* masks) {
+  ODT_CHECK(logits && labels && valid && masks, "odt_op_mask_select: null argument");
+  ODT_CHECK(B >= 1 && per_image >= 1 && ld >= 1, "odt_op_mask_select: bad sizes");
+  const int R = B * per_image;
+  for (int b = 0; b < B; ++b) {
+    ODT_CHECK(valid[b] >= 0 && valid[b] <= per_image, "odt_op_mask_select: valid out of range");
+    for (int j = 0; j < valid[b]; ++j)
+      ODT_CHECK(labels[b * per_image + j] >= 1 && labels[b * per_image + j] <= ld, "odt_op_mask_select: label out of range");
+  }
+  if (set_dev(device)) return 1;
+  GBufs g;
+  MaskSelectParams p; std::memset(&p, 0, sizeof(p));
+  float* dlog; int *dlab, *dval;
+  if (g.alloc("logits", (size_t)R * 14 * 14 * 4 * ld, &dlog, -1, logits) || g.alloc("labels", (size_t)R, &dlab, -1, labels) ||
+      g.alloc("valid", (size_t)B, &dval, -1, valid) || g.alloc("masks", (size_t)R * 784, &p.masks)) return 1;
+  p.logits = dlog; p.ld = ld; p.labels = dlab; p.valid = dval; p.B = B; p.per_image = per_image;
+  if (launch_mask_select(p, nullptr)) return 1;
+  if (g.check("odt_op_mask_select")) return 1;
+  return get_dev(masks, p.masks, (size_t)R * 784);
+}
+
 int odt_op_detections(int device, int graph, int B, int K, int C, const float* cls_logits,
                       const float* box_logits, const float* props, const int32_t* nprops, int img_h, int img_w,
                       const float* reg_weights, float decode_clip, float score_thresh, float nms_thresh,

@@ -89,6 +89,11 @@ __global__ void __launch_bounds__(256) roi_align_kernel(RoiAlignParams p, int B)
   // crop_and_resize_op.cc
   const float hs = (by2 - by1) * fH1 / (float)(CS - 1);
   const float ws = (bx2 - bx1) * fW1 / (float)(CS - 1);
+  // first sample and sample step per axis.  A level one pixel high (wide) has fH1 (fW1) == 0 and the round trip through
+  // the normalised box above divides by it; analytically that round trip is the identity, so such an axis takes the
+  // box's own first sample and step (see RoiAlignParams).  Workgroup-uniform; axes of two or more pixels are as before.
+  const float fy0 = H == 1 ? y0 + sh / 2.0f - 0.5f : by1 * fH1, fys = H == 1 ? sh : hs;
+  const float fx0 = W == 1 ? x0 + sw / 2.0f - 0.5f : bx1 * fW1, fxs = W == 1 ? sw : ws;
   const float* feat = fbase + (size_t)b * ah * aw * ldc;
   const int cq = threadIdx.x & 15, c = cb + cq * 4;      // first of this thread's four channels
   const int nch = p.C - cb < kRoiCB ? p.C - cb : kRoiCB;        // channels of this block
@@ -106,7 +111,7 @@ __global__ void __launch_bounds__(256) roi_align_kernel(RoiAlignParams p, int B)
       bool vy[2];
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
-        const float in_y = by1 * fH1 + (float)(2 * oy + k) * hs;
+        const float in_y = fy0 + (float)(2 * oy + k) * fys;
         vy[k] = !(in_y < 0.f || in_y > fH1);
         const float iy = vy[k] ? in_y : 0.f;
         top[k] = (int)floorf(iy);
@@ -116,7 +121,7 @@ __global__ void __launch_bounds__(256) roi_align_kernel(RoiAlignParams p, int B)
       f32x4 v[2][2];
 #pragma unroll
       for (int qx = 0; qx < 2; ++qx) {
-        const float in_x = bx1 * fW1 + (float)(2 * ox + qx) * ws;
+        const float in_x = fx0 + (float)(2 * ox + qx) * fxs;
         const bool vx = !(in_x < 0.f || in_x > fW1);
         const float ix = vx ? in_x : 0.f;
         const int lef = (int)floorf(ix), rig = (int)ceilf(ix);

@@ -210,6 +210,52 @@ def roi_align(feats_nhwc, strides, boxes, box_ind, lib=None, device=0):
   return out, pooled
 
 
+SENTINEL_BITS = 0x7F7F7F7F      # what an output element no kernel wrote reads back as (odt_op_roi_align_plan, EfficientDet ops)
+
+
+def roi_align_plan(allocs, views, Cc, strides, boxes, per_image, count=None, levels=None, level0=2, out_size=7, pack_rows=0,
+                   want_amax=False, nhwc=False, nchw=False, pooled=False, lib=None, device=0):
+  """The ROIAlign kernel with the parameters the plans give it (one launch_roi_align).  allocs = list of 1..5 whole
+  allocations [B,alloc_h,alloc_w,ldc]; views = [(h, w)] of each that the kernel may read, with the first Cc channels;
+  boxes [B * per_image,4]; count [B] or None; levels [B * per_image] or None (FPN rule).  nhwc / nchw / pooled choose the
+  outputs.  Returns dict(nhwc [R,o,o,C], nchw [R,C,o,o], pooled [R,C], amax uint32 float bits), None where not asked for;
+  rows the kernel did not write hold SENTINEL_BITS."""
+  lib = _L(lib)
+  al = [f32(a) for a in allocs]
+  L = len(al); B = al[0].shape[0]
+  dims = i32([[h, w, a.shape[1], a.shape[2], a.shape[3]] for (h, w), a in zip(views, al)])
+  fp = (c_float_p * L)(*[fptr(a) for a in al])
+  st = f32(strides); bx = f32(boxes).reshape(-1, 4)
+  R = B * per_image
+  assert bx.shape[0] == R and st.size == L
+  cnt = i32(count) if count is not None else None
+  lv = i32(levels) if levels is not None else None
+  assert cnt is None or cnt.size == B
+  assert lv is None or lv.size == R
+  o = out_size if out_size else 7
+  out_nhwc = np.empty((R, o, o, Cc), np.float32) if nhwc else None
+  out_nchw = np.empty((R, Cc, o, o), np.float32) if nchw else None
+  out_pool = np.empty((R, Cc), np.float32) if pooled else None
+  amax = np.zeros(1, np.uint32)
+  lib.check(lib.dll.odt_op_roi_align_plan(device, B, Cc, L, iptr(dims), fp, fptr(st), fptr(bx), per_image,
+                                          iptr(cnt) if cnt is not None else None, iptr(lv) if lv is not None else None,
+                                          level0, out_size, int(pack_rows), int(want_amax), _p(out_nhwc), _p(out_nchw),
+                                          _p(out_pool), amax.ctypes.data_as(C.POINTER(C.c_uint32))))
+  return dict(nhwc=out_nhwc, nchw=out_nchw, pooled=out_pool, amax=amax[0] if want_amax else None)
+
+
+def mask_select(logits, labels, valid, per_image, lib=None, device=0):
+  """mask head tail (launch_mask_select): logits [B * per_image,14,14,4,ld], labels [B * per_image] 1-based, valid [B]
+  -> masks [B * per_image,28,28]."""
+  lib = _L(lib)
+  lg = f32(logits); lb = i32(labels); vd = i32(valid)
+  R, ld, B = lg.shape[0], lg.shape[4], vd.size
+  assert lg.shape[1:4] == (14, 14, 4) and R == B * per_image and lb.size == R
+  masks = np.empty((R, 28, 28), np.float32)
+  lib.check(lib.dll.odt_op_mask_select(device, fptr(lg), ld, iptr(lb), iptr(vd), B, per_image, fptr(masks)))
+  return masks
+
+
 def detections(graph, cls_logits, box_logits, props, nprops, img_hw, reg_weights, decode_clip,
                score_thresh, nms_thresh, per_im, lib=None, device=0):
   """inference tail (reference models.py:828-843, :1258-1304 / :2924-2976).
