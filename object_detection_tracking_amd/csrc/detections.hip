@@ -55,20 +55,60 @@ __global__ void __launch_bounds__(256) head_post_kernel(DetectParams p) {
 }
 
 // ---- K12/K13: per-(class, image) NMS ---------------------------------------------------------
+// Writes one class list of image b.  keep[0..nk) are the NMS picks (ascending positions in the score-sorted candidates,
+// roi[] maps a position to its RoI); candidates from position npos on have score 0.
+// ODT_GRAPH_MULTI: combined_non_max_suppression runs over the M = sum(nprops) rows of the whole batch, where the rows of
+// the other images are zero-score, zero-box slots (score_threshold -inf: legal picks; zero area: they neither suppress nor
+// are suppressed).  Candidates go by (score desc, row asc) and the rows of images q < b lie before image b's own rows, so
+// with scores >= 0 the class list is, capped at per_im throughout: the picks with a positive score, up to
+// S_lo = sum nprops[q < b] slots, the zero-score picks, up to S_hi = sum nprops[q > b] slots.  Greedy NMS with a smaller
+// cap selects a prefix of the picks, so the cap is applied here.  A slot is stored as RoI -1.
+__device__ __forceinline__ void write_class_list(const DetectParams& p, int b, int c, const int* roi, const int* keep,
+                                                 int nk, int npos) {
+  const int tid = threadIdx.x, per = p.per_im, Cm1 = p.C - 1;
+  int* out = p.cls_keep + ((size_t)b * Cm1 + c) * per;
+  int npk = nk, mid = 0, nz = 0, tail = 0;
+  if (p.graph == 1) {
+    int s_lo = 0, s_hi = 0;
+    for (int q = 0; q < p.B; ++q) {
+      if (q < b) s_lo += p.nprops[q];
+      if (q > b) s_hi += p.nprops[q];
+    }
+    int lo = 0, hi = nk;                       // picks with a positive score: keep[] ascends
+    while (lo < hi) {
+      const int m = (lo + hi) >> 1;
+      if (keep[m] < npos) lo = m + 1; else hi = m;
+    }
+    npk = lo;
+    mid = s_lo < per - npk ? s_lo : per - npk;
+    nz = nk - npk < per - npk - mid ? nk - npk : per - npk - mid;
+    tail = s_hi < per - npk - mid - nz ? s_hi : per - npk - mid - nz;
+  }
+  for (int i = tid; i < npk; i += blockDim.x) out[i] = roi[keep[i]];
+  for (int i = tid; i < mid; i += blockDim.x) out[npk + i] = -1;
+  for (int i = tid; i < nz; i += blockDim.x) out[npk + mid + i] = roi[keep[npk + i]];
+  for (int i = tid; i < tail; i += blockDim.x) out[npk + mid + nz + i] = -1;
+  if (tid == 0) p.cls_count[b * Cm1 + c] = npk + mid + nz + tail;
+}
+
 __global__ void __launch_bounds__(kSelThreads) class_nms_kernel(DetectParams p) {
   __shared__ __attribute__((aligned(16))) char raw[sizeof(NmsScratch)];
   __shared__ int s_roi[kMaxTopK];
   __shared__ int s_wave[kSelWaves + 1];
+  __shared__ int s_npos;
   NmsScratch& s = *reinterpret_cast<NmsScratch*>(raw);
   unsigned long long* keys = s.mask;                              // alias: dead before the bitmask
   const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int n = p.nprops[b];
   const int Cm1 = p.C - 1;
+  if (tid == 0) s_npos = 0;
+  __syncthreads();
   float prob = 0.f;
   int cand = 0;
   if (tid < n) {
     prob = p.probs[((size_t)b * p.K + tid) * p.C + c + 1];
     cand = (p.graph == 0) ? (prob > p.score_thresh) : 1;
+    if (cand && prob > 0.f) atomicAdd(&s_npos, 1);
   }
   // candidates first, by (prob desc, roi asc); non-candidates get small unique keys
   keys[tid] = cand ? make_key64(prob, (unsigned)tid) : (unsigned long long)(kMaxTopK - tid);
@@ -88,10 +128,7 @@ __global__ void __launch_bounds__(kSelThreads) class_nms_kernel(DetectParams p) 
   }
   __syncthreads();
   block_nms(ncand, p.per_im, p.nms_thresh, s);
-  const int nk = s.nkeep;
-  int* out = p.cls_keep + ((size_t)b * Cm1 + c) * p.per_im;
-  for (int i = tid; i < nk; i += blockDim.x) out[i] = s_roi[s.keep[i]];
-  if (tid == 0) p.cls_count[b * Cm1 + c] = nk;
+  write_class_list(p, b, c, s_roi, s.keep, s.nkeep, s_npos);
 }
 
 // K > 1024 (select_device.hpp: paneled walk): the same candidates in the same order, any number of RoIs up to kMaxTopKBig
@@ -107,19 +144,20 @@ struct ClassBoxAt {
 __global__ void __launch_bounds__(kSelThreads) class_nms_big_kernel(DetectParams p) {
   __shared__ __attribute__((aligned(16))) char raw[sizeof(NmsBigScratch)];
   __shared__ int s_roi[kMaxTopKBig];
-  __shared__ int s_ncand;
+  __shared__ int s_ncand, s_npos;
   NmsBigScratch& s = *reinterpret_cast<NmsBigScratch*>(raw);
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(s.kbox);     // dead before the walk keeps its first box
   const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int n = p.nprops[b];
   const int Cm1 = p.C - 1;
-  if (tid == 0) s_ncand = 0;
+  if (tid == 0) { s_ncand = 0; s_npos = 0; }
   __syncthreads();
   for (int t = tid; t < n; t += blockDim.x) {
     const float prob = p.probs[((size_t)b * p.K + t) * p.C + c + 1];
     const int cand = (p.graph == 0) ? (prob > p.score_thresh) : 1;
     keys[t] = cand ? make_key64(prob, (unsigned)t) : 0ull;       // real keys are > 0 (inverted index in the low word)
     if (cand) atomicAdd(&s_ncand, 1);
+    if (cand && prob > 0.f) atomicAdd(&s_npos, 1);
   }
   __syncthreads();
   // candidates by (prob desc, roi asc)
@@ -134,10 +172,7 @@ __global__ void __launch_bounds__(kSelThreads) class_nms_big_kernel(DetectParams
   const int ncand = s_ncand;
   block_nms_paneled(ncand, p.per_im, p.nms_thresh,
                     ClassBoxAt{p.dec_boxes + ((size_t)b * p.K * Cm1 + c) * 4, s_roi, Cm1 * 4}, s);
-  const int nk = s.nkeep;
-  int* out = p.cls_keep + ((size_t)b * Cm1 + c) * p.per_im;
-  for (int i = tid; i < nk; i += blockDim.x) out[i] = s_roi[s.keep[i]];
-  if (tid == 0) p.cls_count[b * Cm1 + c] = nk;
+  write_class_list(p, b, c, s_roi, s.keep, s.nkeep, s_npos);
 }
 
 // ---- final selection: top result_per_im over the union (models.py:1288-1301 / :2959-2973) ----
@@ -158,8 +193,8 @@ __global__ void __launch_bounds__(kSelThreads) final_select_kernel(DetectParams 
   for (int e = tid; e < Cm1 * per; e += blockDim.x) {
     const int c = e / per, i = e - c * per;
     if (i < p.cls_count[b * Cm1 + c]) {
-      const int roi = p.cls_keep[((size_t)b * Cm1 + c) * per + i];
-      s_prob[s_off[c] + i] = p.probs[((size_t)b * p.K + roi) * p.C + c + 1];
+      const int roi = p.cls_keep[((size_t)b * Cm1 + c) * per + i];      // -1: a zero slot of another image (MULTI)
+      s_prob[s_off[c] + i] = roi < 0 ? 0.f : p.probs[((size_t)b * p.K + roi) * p.C + c + 1];
       s_code[s_off[c] + i] = e;
     }
   }
@@ -183,47 +218,26 @@ __global__ void __launch_bounds__(kSelThreads) final_select_kernel(DetectParams 
     if (rank < per) {
       const int c = mc / per, i = mc - c * per;
       const int roi = p.cls_keep[((size_t)b * Cm1 + c) * per + i];
-      const float* src = p.dec_boxes + (((size_t)b * p.K + roi) * Cm1 + c) * 4;
       float* ob = p.out_boxes + ((size_t)b * per + rank) * 4;
-      ob[0] = src[0]; ob[1] = src[1]; ob[2] = src[2]; ob[3] = src[3];
+      if (roi < 0) {
+        ob[0] = 0.f; ob[1] = 0.f; ob[2] = 0.f; ob[3] = 0.f;
+      } else {
+        const float* src = p.dec_boxes + (((size_t)b * p.K + roi) * Cm1 + c) * 4;
+        ob[0] = src[0]; ob[1] = src[1]; ob[2] = src[2]; ob[3] = src[3];
+      }
       p.out_probs[(size_t)b * per + rank] = my;
       p.out_labels[(size_t)b * per + rank] = c + 1;
     }
   }
-  // Padding.  SINGLE: rows >= nreal are zero and not counted.  MULTI: the zero-score slots of
-  // the other images' RoIs are legal picks of combined_non_max_suppression (score_threshold
-  // -inf): class c can add min(per - kept_c, slots) of them; they sort after every real
-  // detection, by class.
-  int slots = 0;
-  if (p.graph == 1)
-    for (int q = 0; q < p.B; ++q) slots += (q == b) ? 0 : p.nprops[q];
-  int valid = nreal;
+  // Padding: rows >= nreal are zero and not counted.  (MULTI: the zero slots of the other images that
+  // combined_non_max_suppression picks are members of the class lists -- write_class_list -- and were merged above.)
   for (int r = nreal + tid; r < per; r += blockDim.x) {
     float* ob = p.out_boxes + ((size_t)b * per + r) * 4;
     ob[0] = 0.f; ob[1] = 0.f; ob[2] = 0.f; ob[3] = 0.f;
     p.out_probs[(size_t)b * per + r] = 0.f;
-    int label = 0;
-    if (p.graph == 1) {
-      int run = nreal;
-      for (int c = 0; c < Cm1 && label == 0; ++c) {
-        int extra = per - p.cls_count[b * Cm1 + c];
-        if (extra > slots) extra = slots;
-        if (r < run + extra) label = c + 1;
-        run += extra;
-      }
-    }
-    p.out_labels[(size_t)b * per + r] = label;
+    p.out_labels[(size_t)b * per + r] = 0;
   }
-  if (p.graph == 1) {
-    int run = nreal;
-    for (int c = 0; c < Cm1; ++c) {
-      int extra = per - p.cls_count[b * Cm1 + c];
-      if (extra > slots) extra = slots;
-      run += extra;
-    }
-    valid = run < per ? run : per;
-  }
-  if (tid == 0) p.out_valid[b] = valid;
+  if (tid == 0) p.out_valid[b] = nreal;
 }
 
 }  // namespace

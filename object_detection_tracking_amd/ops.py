@@ -277,7 +277,9 @@ def detections(graph, cls_logits, box_logits, props, nprops, img_hw, reg_weights
 def class_nms(graph, boxes, scores, per_im, iou_thresh, score_thresh=0.0, ncand=None, lib=None, device=0):
   """The selection half of the tail on caller-supplied data: per-class NMS + merged top ``per_im``
   (tf.image.combined_non_max_suppression for graph ODT_GRAPH_MULTI, nms_return_masks + fastrcnn_predictions for
-  ODT_GRAPH_SINGLE).  boxes [B,N,C,4] (or [B,N,1,4], shared by the classes), scores [B,N,C].
+  ODT_GRAPH_SINGLE).  boxes [B,N,C,4] (or [B,N,1,4], shared by the classes), scores [B,N,C]; ncand [B]: rows of each
+  image that are real (default N).  ODT_GRAPH_MULTI scores must be >= 0 (they come from a softmax): the kernels place
+  the other images' zero-score padding slots among a class's candidates by that assumption.
   Returns (boxes [B,per_im,4], scores [B,per_im], classes [B,per_im] 0-based, valid [B])."""
   lib = _L(lib)
   sc = f32(scores); B, N, Cn = sc.shape

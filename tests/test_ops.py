@@ -226,7 +226,7 @@ def _oracle_proposals_multi(logits, deltas, anchors, img_hw, K, thr, clip):
   return out
 
 
-@pytest.mark.parametrize("K", [16, 100])
+@pytest.mark.parametrize("K", [16, 100, 1100])      # 1100: P2 has 2304 anchors -- rpn_select_kernel rounds, rpn_nms_big_kernel, rpn_merge_kernel<kMaxTopKBig>
 def test_proposals_single(backend, K):
   name, lib = backend
   rng = np.random.default_rng(K)
@@ -264,14 +264,13 @@ def test_proposals_multi_chunk_level(backend):
 
 
 @pytest.mark.parametrize("neg_shift", [0.0, 2.5])
-def test_proposals_multi_zero_padding_quirk(backend, neg_shift):
+def test_proposals_multi_zero_padding_quirk(backend, neg_shift, K=40):
   """Multibatch graph: NMS output is zero-padded to K per level and the padding (score 0)
   outranks every negative logit in the cross-level top-k (reference models.py:2487-2520)."""
   name, lib = backend
   rng = np.random.default_rng(7)
   img_hw = (96, 128)
   levels = [(24, 32), (12, 16), (6, 8), (3, 4), (2, 2)]
-  K = 40
   rpn, anchors, logits, deltas = _proposal_inputs(rng, 2, levels, img_hw, neg_shift)
   clip = float(np.log(256 / 16.0))
   props, nprops = ops.proposals(ODT_GRAPH_MULTI, rpn, anchors, img_hw, K, 0.7, clip, lib=lib)
@@ -281,6 +280,12 @@ def test_proposals_multi_zero_padding_quirk(backend, neg_shift):
     np.testing.assert_allclose(props[b, :nprops[b]], ref[b], rtol=0, atol=1e-4)
   if neg_shift > 0:
     assert nprops.min() < K      # the quirk actually bit
+
+
+def test_proposals_multi_zero_padding_quirk_k1100(backend):
+  """The same over two images at K = 1100: P2 has 2304 anchors, so its top-k, NMS and the cross-level merge run the
+  K > 1024 kernels (rpn_select_kernel rounds, rpn_nms_big_kernel, rpn_merge_kernel<kMaxTopKBig>)."""
+  test_proposals_multi_zero_padding_quirk(backend, 2.5, K=1100)
 
 
 def test_roi_align(backend):
