@@ -343,6 +343,13 @@ bool conv_block_fits(const ConvParams& c1, const ConvParams& c2) {
   return c1_ok && c2_ok;
 }
 
+void conv_block_fuse(ConvParams& c2, const ConvParams& c1, const void* img_p) {
+  c2.b_in = c1.in; c2.b_in_ldc = c1.in_ldc; c2.b_cin = c1.Cin; c2.b_wt = c1.wt_split; c2.b_chinv = c1.h2_chinv;
+  c2.b_bias = c1.bias; c2.b_in_amax = c1.in_amax; c2.b_wt2 = img_p;
+  c2.in = c1.in; c2.in_amax = c1.in_amax;        // (conv1's output does not exist: the record names real memory only)
+  c2.debug |= c1.debug & 0x100;
+}
+
 int launch_bottleneck_block(const ConvParams& p, const ConvParams* dev, hipStream_t stream) {
   ODT_CHECK(p.b_in != nullptr && p.b_wt != nullptr && p.b_wt2 != nullptr && p.b_chinv != nullptr && p.b_bias != nullptr && p.f_wt != nullptr &&
                 p.f_out != nullptr && p.h2_chinv != nullptr && p.Cin == 64 && p.Cout == 64 && p.b_cin == 256 && p.f_cout == 256 && p.kh == 3 && p.kw == 3 &&

@@ -418,7 +418,7 @@ const float* conv_h2_chinv(const void* img, int Cout, int K) {
 }
 
 int conv_make_h2_weights(const ConvParams& p, void* img_dev, hipStream_t stream) {
-  const int K = p.kh * p.kw * p.Cin + (p.in2 != nullptr ? p.Cin2 : 0);
+  const int K = conv_k(p);
   const int bn = conv_variant_row(p.variant).bn;
   ODT_CHECK((bn == 256 || bn == 128 || bn == 64) && p.Cin % 32 == 0 && (p.in2 == nullptr || p.Cin2 % 32 == 0) && cout_padded(p.Cout) % bn == 0,
             "conv_make_h2_weights: 256- / 128- / 64-wide n-tiles and 32-channel slices required");
@@ -475,6 +475,15 @@ bool conv_h2f_fusable(const ConvParams& a, const ConvParams& b) {
                     b.relu <= 1 && b.nlvl <= 1 && b.head_wt == nullptr && b.splitk <= 1 && b.wt_split != nullptr && conv_variant_row(b.variant).family == CF_H2 &&
                     b.f_wt == nullptr && (double)b.B * b.Ho * b.Wo * b.out_ldc * 4.0 < 2147483648.0;
   return a_ok && b_ok;
+}
+
+void conv_h2f_fuse(ConvParams& a, const ConvParams& b, const void* img_f) {
+  conv_use_variant(a, conv_variant_fused_tail(a.variant), a.splitk, a.reduce_blocks);
+  a.f_wt = img_f; a.f_chinv = conv_h2f_chinv(img_f, b.Cout, b.Cin); a.f_bias = b.bias;
+  a.f_res = b.res_mode != 0 ? b.res : nullptr; a.f_res_ldc = b.res_ldc;
+  a.f_out = b.out; a.f_out_ldc = b.out_ldc; a.f_cout = b.Cout; a.f_relu = b.relu; a.f_out_amax = b.out_amax;
+  a.debug |= b.debug & 0x400;           // the residual's non-temporal hint travels with it
+  a.out = nullptr; a.out_amax = nullptr;
 }
 
 int launch_tensor_amax(const float* x, size_t n, unsigned* slot, hipStream_t stream) {

@@ -176,7 +176,7 @@ void conv_use_variant(ConvParams& p, int variant, int splitk, int reduce_blocks)
 }
 
 // ---- shape predicates (selection and validation share them) ------------------------------------------------------------
-static int conv_k(const ConvParams& p) { return p.kh * p.kw * p.Cin + (p.in2 != nullptr ? p.Cin2 : 0); }
+int conv_k(const ConvParams& p) { return p.kh * p.kw * p.Cin + (p.in2 != nullptr ? p.Cin2 : 0); }
 static long conv_tiles(const ConvParams& p, int bm, int bn) { return (((long)p.B * p.Ho * p.Wo + bm - 1) / bm) * (cout_padded(p.Cout) / bn); }
 
 // stride-1 KH x 3 convs over rows of the output's pitch: the kw taps share a staged run of pixels
@@ -500,7 +500,7 @@ int conv_make_split_weights(const ConvParams& p, void* img_dev, hipStream_t stre
   ODT_CHECK(kscale == nullptr || (p.kh == 1 && p.kw == 1 && p.in2 == nullptr), "conv_make_split_weights: a folded gate belongs to a single-source 1x1 conv");
   const ConvKernelRow& r = conv_variant_row(p.variant);
   const int bn = r.bn;
-  const int K = p.kh * p.kw * p.Cin + (p.in2 != nullptr ? p.Cin2 : 0);
+  const int K = conv_k(p);
   ODT_CHECK(r.launch != nullptr && r.family != CF_F32 && K % 32 == 0,
             "conv_make_split_weights: Cout % 64 == 0, K % 32 == 0 and a chosen kernel family required");
   if (r.family == CF_H2) {
@@ -518,6 +518,11 @@ int conv_make_split_weights(const ConvParams& p, void* img_dev, hipStream_t stre
   }
   ODT_HIP(hipGetLastError());
   return 0;
+}
+
+void conv_attach_weights(ConvParams& p, const void* img) {
+  p.wt_split = img;
+  if (conv_variant_row(p.variant).family == CF_H2) p.h2_chinv = conv_h2_chinv(img, p.Cout, conv_k(p));
 }
 
 }  // namespace odt

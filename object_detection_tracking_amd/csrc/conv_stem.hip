@@ -295,6 +295,11 @@ bool conv_stem_fits(const ConvParams& p) {
          p.out_ldc >= 64 && p.out_ldc % 4 == 0;
 }
 
+void conv_stem_fuse(ConvParams& p, float* pooled, int H, int W, int ldc) {
+  p.out = pooled; p.out_H = H; p.out_W = W; p.out_ldc = ldc;
+  conv_use_variant(p, CV_H2_STEM, p.splitk, p.reduce_blocks);
+}
+
 int conv_stem_grid(const ConvParams& p, unsigned* grid) {
   // one persistent workgroup per CU of the CURRENT device (handles on different devices / partitions differ; several
   // host threads may launch at once): a per-device table, each slot written once with a value that depends on the device

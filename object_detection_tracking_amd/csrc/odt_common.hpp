@@ -266,7 +266,10 @@ bool conv_kwr_fits(const ConvParams& p);           // the kw-reuse kernels: stri
 bool conv_h2_sources_ok(const ConvParams& p);      // fp16x2 allowed for this layer: recorded range(s), 32-channel slices
 bool conv_h2d_fits(const ConvParams& p);           // conv_h2d.hip: dense same-size 1x1 with at least two double stages
 bool conv_stem_fits(const ConvParams& p);          // conv_stem.hip: the plan's conv0 on 64-wide fp16x2 tiles
+// THE record rewrite behind conv_stem_fits (the plan's fuse_stem, odt_op_stem): p writes the pooled map and runs CV_H2_STEM
+void conv_stem_fuse(ConvParams& p, float* pooled, int H, int W, int ldc);
 int conv_stem_grid(const ConvParams& p, unsigned* grid);   // one persistent workgroup per CU of the current device
+int conv_k(const ConvParams& p);   // the GEMM's reduction length: kh * kw * Cin (+ Cin2)
 size_t conv_split_weight_bytes(int Cout, int K);
 int conv_split_bn(int Cout);   // n-tile width of the split configuration for this Cout (0: none)
 int conv_split_bm(int Cout);
@@ -276,6 +279,8 @@ int conv_split_bm(int Cout);
 int conv_make_split_weights(const ConvParams& p, void* img_dev, hipStream_t stream, const float* wt_src = nullptr,
                             const float* kscale = nullptr);
 int conv_scale_weights(const float* wt, const float* kscale, int Cout, int K, float* out, hipStream_t stream);
+// points p at its finished image: wt_split and, for the CF_H2 rows, h2_chinv (behind the pieces of p's own Cout x conv_k)
+void conv_attach_weights(ConvParams& p, const void* img);
 // fp16x2 pieces (conv_h2.hip; CF_H2 rows): the image (conv_make_split_weights builds it) carries the per-column
 // inverse scales behind the pieces -- ConvParams::h2_chinv must point there; launch_tensor_amax records the |max| of a dense
 // array for a source tensor no producer recorded one for (stand-alone calls)
@@ -289,10 +294,17 @@ size_t conv_h2f_weight_bytes(int Cout, int K);
 const float* conv_h2f_chinv(const void* img, int Cout, int K);
 int conv_make_h2f_weights(const float* wt, int Cout, int K, void* img_dev, hipStream_t stream);
 bool conv_h2f_fusable(const ConvParams& a, const ConvParams& b);   // a: the KH x 3 producer, b: the 1x1 conv reading a.out
+// THE record rewrite behind conv_h2f_fusable (the plan's fuse_bottleneck_tails, odt_op_bottleneck_tail / _block): a becomes the
+// fused record -- the fused-tail row of its own image (split-K choices kept), every f_* field from b and b's image `img_f`
+// (conv_make_h2f_weights), the residual's non-temporal bit (debug & 0x400) with it; a's own output and range slot are gone
+void conv_h2f_fuse(ConvParams& a, const ConvParams& b, const void* img_f);
 // whole identity bottleneck in one kernel (conv_block.hip): a 64-wide 3x3 conv's image with k in the order conv1's accumulator
 // registers hold it (same size and row scales as conv_make_h2_weights'), the shape test, the launcher of an OP_BLOCK record
 int conv_make_h2p_weights(const ConvParams& p, void* img_dev, hipStream_t stream);
 bool conv_block_fits(const ConvParams& c1, const ConvParams& c2);    // c1: the 1x1 conv in front, c2: the 3x3 conv carrying the fused tail
+// THE record rewrite behind conv_block_fits (the plan's fuse_bottleneck_blocks, odt_op_bottleneck_block): the b_* fields from c1
+// and c2's patch-order image `img_p` (conv_make_h2p_weights); c2 reads c1's input and range, and walks K as c1 did (debug & 0x100)
+void conv_block_fuse(ConvParams& c2, const ConvParams& c1, const void* img_p);
 int launch_bottleneck_block(const ConvParams& p, const ConvParams* dev, hipStream_t stream);
 size_t conv_split_partial_bytes(const ConvParams& p);   // scratch a split-K conv needs (0: none)
 

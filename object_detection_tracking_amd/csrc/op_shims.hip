@@ -1,5 +1,7 @@
 // Stand-alone op entry points of the C ABI (include/odt.h: odt_op_*, odt_nn_cosine): host pointers in and out, each
-// runs exactly the kernels the forward uses -- what the staged parity tests call.
+// runs exactly the kernels the forward uses -- what the staged parity tests call.  The fusion shims (odt_op_bottleneck_tail,
+// odt_op_bottleneck_block, odt_op_stem) turn their records into the fused ones with the functions the plan's fuse_* passes call
+// (conv_h2f_fuse, conv_block_fuse, conv_stem_fuse: odt_common.hpp), so a test of a shim tests the plan's rewrite.
 #include <functional>
 
 #include "odt_model.hpp"
@@ -47,6 +49,42 @@ void conv_report(int variant, int splitk, int reduce_blocks, int* out, char* nam
   }
 }
 
+// a conv record over dense tensors: in [B,H,W,Cin] -> out [B,Ho,Wo,Cout], wt [Cout][kh][kw][Cin].  Residual, output offset and
+// second source: the callers that have one set them.
+ConvParams dense_conv(const float* in, const float* wt, const float* bias, float* out, int B, int H, int W, int Cin, int Ho, int Wo,
+                      int Cout, int kh, int kw, int stride, int dil, int pad_t, int pad_l, int relu) {
+  ConvParams p; std::memset(&p, 0, sizeof(p));
+  p.in = in; p.wt = wt; p.bias = bias; p.out = out;
+  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.in_ldc = Cin; p.in_Ha = H; p.in_Wa = W; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout;
+  p.kh = kh; p.kw = kw; p.stride = stride; p.dil = dil; p.pad_t = pad_t; p.pad_l = pad_l;
+  p.out_H = Ho; p.out_W = Wo; p.out_ldc = Cout; p.relu = relu;
+  return p;
+}
+// ... the bottleneck's convs: k x k, stride 1, 'SAME' for dilation dil, same size out
+ConvParams same_conv(const float* in, const float* wt, const float* bias, float* out, int B, int H, int W, int Cin, int Cout, int k,
+                     int dil, int relu) {
+  return dense_conv(in, wt, bias, out, B, H, W, Cin, H, W, Cout, k, k, 1, dil, dil * (k - 1) / 2, dil * (k - 1) / 2, relu);
+}
+
+// HWIO weights [kh][kw][Cin][Cout] in the kernels' order [Cout][kh][kw][Cin] (a 1x1 conv's "IO" matrix: kh = kw = 1)
+std::vector<float> ohwi(const float* hwio, int kh, int kw, int Cin, int Cout) {
+  std::vector<float> w((size_t)Cout * kh * kw * Cin);
+  for (int t = 0; t < kh * kw; ++t) for (int i = 0; i < Cin; ++i) for (int o = 0; o < Cout; ++o)
+    w[((size_t)o * kh * kw + t) * Cin + i] = hwio[((size_t)t * Cin + i) * Cout + o];
+  return w;
+}
+
+// this record runs row `variant` on the fp16x2 kernels: its sources' and its output's range slots, the derived fields, its
+// weight image in img
+int use_h2_row(ConvParams& p, int variant, const unsigned* in_amax, unsigned* out_amax, Tmp<float>& img) {
+  conv_use_variant(p, variant);
+  p.in_amax = in_amax; p.out_amax = out_amax;
+  conv_prepare(p);
+  if (img.alloc((conv_split_weight_bytes(p.Cout, conv_k(p)) + 3) / 4) || conv_make_split_weights(p, img.d, nullptr)) return 1;
+  conv_attach_weights(p, img.d);
+  return 0;
+}
+
 // one stand-alone conv (odt_op_conv2d*: dense tensors, null stream) as a plan would run it: the library's policy under the
 // call's knobs, a temporary weight image / split-K scratch / input range where the split kernels take it, a finished record
 int run_conv(ConvParams q, const Knobs& kn) {
@@ -65,8 +103,7 @@ int run_conv(ConvParams q, const Knobs& kn) {
   const ConvPolicy pol = conv_policy_with_knobs(conv_policy_default(), kn);
   ConvChoice ch = conv_select(q, pol, kn);
   if (conv_variant_row(ch.variant).family != CF_F32) {
-    const int Ksp = q.kh * q.kw * q.Cin + (q.in2 != nullptr ? q.Cin2 : 0);
-    ODT_HIP(hipMalloc(&tmp.img, conv_split_weight_bytes(q.Cout, Ksp)));
+    ODT_HIP(hipMalloc(&tmp.img, conv_split_weight_bytes(q.Cout, conv_k(q))));
     if (pol.family == 2 && q.in_amax == nullptr) {      // fp16x2 pieces need the sources' |max|: nobody recorded it for a stand-alone call
       // (the scan covers the whole allocation B x in_Ha x in_Wa x in_ldc of a source: a stand-alone caller hands over
       // dense tensors -- odt_op_conv2d* -- so this is the logical view; a sliced view would have to bring its own range)
@@ -82,8 +119,7 @@ int run_conv(ConvParams q, const Knobs& kn) {
     }
     conv_use_variant(q, ch.variant, ch.splitk, ch.reduce_blocks);
     if (conv_make_split_weights(q, tmp.img, nullptr)) return 1;
-    if (conv_variant_row(q.variant).family == CF_H2) q.h2_chinv = conv_h2_chinv(tmp.img, q.Cout, Ksp);
-    q.wt_split = tmp.img;
+    conv_attach_weights(q, tmp.img);
     if (conv_split_partial_bytes(q) > 0) ODT_HIP(hipMalloc((void**)&tmp.partial, conv_split_partial_bytes(q)));
     q.partial = tmp.partial;
   }
@@ -92,6 +128,107 @@ int run_conv(ConvParams q, const Knobs& kn) {
   ODT_HIP(hipMalloc((void**)&tmp.rec, sizeof(ConvParams)));
   ODT_HIP(hipMemcpy(tmp.rec, &q, sizeof(ConvParams), hipMemcpyHostToDevice));
   return launch_conv(q, tmp.rec, nullptr);
+}
+
+// ODT_CONV_TRACE report of odt_op_conv2d (tuning aid): per-phase wall-clock (100 MHz) statistics over the workgroups
+int report_conv_trace(Tmp<unsigned long long>& tr, int max_blocks) {
+  std::vector<unsigned long long> t((size_t)max_blocks * 16);
+  if (tr.get(t.data(), t.size())) return 1;
+  unsigned long long t0 = ~0ull, t1 = 0; int nb = 0;
+  double ph[5] = {0, 0, 0, 0, 0};
+  for (int b = 0; b < max_blocks; ++b) {
+    const unsigned long long* q = &t[(size_t)b * 16];
+    if (q[0] == 0) continue;
+    ++nb; if (q[0] < t0) t0 = q[0]; if (q[5] > t1) t1 = q[5];
+    for (int i = 0; i < 5; ++i) ph[i] += (double)(q[i + 1] - q[i]);
+  }
+  printf("[conv trace] blocks=%d span=%.1f us | per block avg us: prologue %.2f  mainloop %.2f  res-issue+stage0 %.2f  "
+         "pass0 lds->stores %.2f  pass1 %.2f | sum %.2f\n", nb, (t1 - t0) / 100.0, ph[0] / nb / 100, ph[1] / nb / 100,
+         ph[2] / nb / 100, ph[3] / nb / 100, ph[4] / nb / 100, (ph[0] + ph[1] + ph[2] + ph[3] + ph[4]) / nb / 100);
+  // concurrency: how many blocks are in the main loop at the midpoint of the launch
+  const unsigned long long mid = t0 + (t1 - t0) / 2; int in_main = 0, in_epi = 0, in_pro = 0;
+  for (int b = 0; b < max_blocks; ++b) {
+    const unsigned long long* q = &t[(size_t)b * 16];
+    if (q[0] == 0) continue;
+    if (mid >= q[0] && mid < q[1]) ++in_pro; else if (mid >= q[1] && mid < q[2]) ++in_main; else if (mid >= q[2] && mid < q[5]) ++in_epi;
+  }
+  {   // first dispatch wave vs the rest
+    double sa[3] = {0, 0, 0}, sb[3] = {0, 0, 0};
+    double pa = 0, pb = 0, ma = 0, mb = 0; int na = 0, nb2 = 0;
+    for (int b = 0; b < max_blocks; ++b) {
+      const unsigned long long* q = &t[(size_t)b * 16];
+      if (q[0] == 0) continue;
+      double* sx = (q[0] - t0 < 500) ? sa : sb;
+      sx[0] += (double)(q[6] - q[0]); sx[1] += (double)(q[7] - q[6]); sx[2] += (double)(q[1] - q[7]);
+      if (q[0] - t0 < 500) { pa += (double)(q[1] - q[0]); ma += (double)(q[2] - q[1]); ++na; }
+      else { pb += (double)(q[1] - q[0]); mb += (double)(q[2] - q[1]); ++nb2; }
+    }
+    printf("[conv trace] first wave (%d blocks): prologue %.2f us, mainloop %.2f us | later (%d blocks): prologue %.2f us, mainloop %.2f us\n",
+           na, na ? pa / na / 100 : 0.0, na ? ma / na / 100 : 0.0, nb2, nb2 ? pb / nb2 / 100 : 0.0, nb2 ? mb / nb2 / 100 : 0.0);
+    if (na && nb2)
+      printf("[conv trace] prologue split (setup / first loads+lds / barrier): first wave %.2f / %.2f / %.2f us, later %.2f / %.2f / %.2f us\n",
+             sa[0] / na / 100, sa[1] / na / 100, sa[2] / na / 100, sb[0] / nb2 / 100, sb[1] / nb2 / 100, sb[2] / nb2 / 100);
+  }
+  printf("[conv trace] at mid-launch: %d blocks in prologue, %d in main loop, %d in epilogue\n", in_pro, in_main, in_epi);
+  {   // placement and per-CU concurrency: for every CU, the fraction of its busy time with 0 / 1 / 2 / 3+
+      // resident workgroups inside the main loop (lockstep shows up as time with 0 in the loop)
+    std::map<unsigned, std::vector<int>> cu_blocks;
+    for (int b = 0; b < max_blocks; ++b) {
+      const unsigned long long* q = &t[(size_t)b * 16];
+      if (q[0] == 0) continue;
+      const unsigned hw = (unsigned)q[8], xcc = (unsigned)q[9] & 0xf;
+      const unsigned cu = (hw >> 8) & 0xf, sh = (hw >> 12) & 1, se = (hw >> 13) & 0x7;
+      cu_blocks[(xcc << 12) | (se << 8) | (sh << 4) | cu].push_back(b);
+    }
+    double frac[4] = {0, 0, 0, 0}; double busy = 0;
+    for (auto& kv : cu_blocks) {
+      std::vector<std::pair<unsigned long long, int>> ev;   // (time, +1/-1) for main-loop occupancy
+      unsigned long long lo = ~0ull, hi = 0;
+      for (int b : kv.second) {
+        const unsigned long long* q = &t[(size_t)b * 16];
+        ev.push_back({q[1], +1}); ev.push_back({q[2], -1});
+        if (q[0] < lo) lo = q[0]; if (q[5] > hi) hi = q[5];
+      }
+      std::sort(ev.begin(), ev.end());
+      unsigned long long prev = lo; int n = 0;
+      for (auto& e : ev) {
+        frac[n > 3 ? 3 : n] += (double)(e.first - prev); prev = e.first; n += e.second;
+      }
+      frac[0] += (double)(hi - prev); busy += (double)(hi - lo);
+    }
+    printf("[conv trace] %zu CUs seen; time share per CU with k workgroups in the main loop: k=0 %.3f  k=1 %.3f  k=2 %.3f  k>=3 %.3f\n",
+           cu_blocks.size(), frac[0] / busy, frac[1] / busy, frac[2] / busy, frac[3] / busy);
+    // dispatch order on XCD 0: which CU did the first blocks land on
+    printf("[conv trace] XCD0 first blocks -> (se,cu,tg): ");
+    for (int b = 0; b < 8 * 40 && b < max_blocks; b += 8) {
+      const unsigned long long* q = &t[(size_t)b * 16];
+      if (q[0] == 0) break;
+      const unsigned hw = (unsigned)q[8];
+      printf("%u.%u.%u ", (hw >> 13) & 7, (hw >> 8) & 0xf, (hw >> 16) & 0xf);
+    }
+    printf("\n");
+  }
+  fflush(stdout);
+  return 0;
+}
+
+// ODT_CONV_TRACE report of odt_op_bottleneck_block (tuning aid): per-phase wall-clock (100 MHz) averages over the tiles
+int report_block_trace(Tmp<unsigned long long>& tr, size_t ntile) {
+  ODT_HIP(hipDeviceSynchronize());
+  std::vector<unsigned long long> t(ntile * 16);
+  if (tr.get(t.data(), t.size())) return 1;
+  double ph[5] = {0, 0, 0, 0, 0};
+  unsigned long long t0 = ~0ull, t1 = 0;
+  for (size_t i = 0; i < ntile; ++i) {
+    const unsigned long long* q = &t[i * 16];
+    ph[0] += (double)(q[1] - q[0]); ph[1] += (double)(q[2] - q[1]); ph[2] += (double)(q[6] - q[2]); ph[3] += (double)(q[3] - q[6]); ph[4] += (double)(q[5] - q[3]);
+    if (q[0] < t0) t0 = q[0];
+    if (q[5] > t1) t1 = q[5];
+  }
+  printf("[block trace] tiles=%zu span=%.1f us | per tile avg us: conv1 loop %.2f  patch %.2f  conv2 %.2f  tail pieces %.2f  conv3 + stores %.2f\n",
+         ntile, (t1 - t0) / 100.0, ph[0] / ntile / 100, ph[1] / ntile / 100, ph[2] / ntile / 100, ph[3] / ntile / 100, ph[4] / ntile / 100);
+  fflush(stdout);
+  return 0;
 }
 
 // device buffers of the EfficientDet op shims (odt_op_dwconv ... odt_op_preprocess_rgb): every one ends in kGuardBytes of
@@ -194,21 +331,15 @@ int odt_op_conv2d(int device, const float* in, int B, int H, int W, int Cin, con
   ODT_CHECK(in && wt_hwio && out, "odt_op_conv2d: null argument");
   if (set_dev(device)) return 1;
   const size_t nin = (size_t)B * H * W * Cin, nout = (size_t)B * (Ho + oy) * (Wo + ox) * Cout;
-  std::vector<float> w((size_t)Cout * kh * kw * Cin), bz(Cout, 0.f);
-  for (int y = 0; y < kh; ++y) for (int x = 0; x < kw; ++x) for (int i = 0; i < Cin; ++i) for (int o = 0; o < Cout; ++o)
-    w[(((size_t)o * kh + y) * kw + x) * Cin + i] = wt_hwio[(((size_t)y * kw + x) * Cin + i) * Cout + o];
+  const std::vector<float> w = ohwi(wt_hwio, kh, kw, Cin, Cout), bz(Cout, 0.f);
   const int rH = res_mode == 2 ? (Ho + 1) / 2 : Ho, rW = res_mode == 2 ? (Wo + 1) / 2 : Wo;
   Tmp<float> di, dw, db, dr, dout;
   if (di.alloc(nin) || dw.alloc(w.size()) || db.alloc(Cout) || dout.alloc(nout) || dout.zero()) return 1;
   if (di.put(in) || dw.put(w.data()) || db.put(bias ? bias : bz.data())) return 1;
   if (res && res_mode) { if (dr.alloc((size_t)B * rH * rW * Cout) || dr.put(res)) return 1; }
-  ConvParams p; std::memset(&p, 0, sizeof(p));
-  p.in = di.d; p.wt = dw.d; p.bias = db.d; p.res = (res && res_mode) ? dr.d : nullptr; p.out = dout.d;
-  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.in_ldc = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout;
-  p.kh = kh; p.kw = kw; p.stride = stride; p.dil = dil; p.pad_t = pad_t; p.pad_l = pad_l;
-  p.out_H = Ho + oy; p.out_W = Wo + ox; p.out_oy = oy; p.out_ox = ox; p.out_ldc = Cout;
-  p.res_mode = p.res ? res_mode : 0; p.res_H = rH; p.res_W = rW; p.res_ldc = Cout; p.relu = relu;
-  p.in_Ha = H; p.in_Wa = W;
+  ConvParams p = dense_conv(di.d, dw.d, db.d, dout.d, B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, dil, pad_t, pad_l, relu);
+  p.out_H = Ho + oy; p.out_W = Wo + ox; p.out_oy = oy; p.out_ox = ox;
+  p.res = (res && res_mode) ? dr.d : nullptr; p.res_mode = p.res ? res_mode : 0; p.res_H = rH; p.res_W = rW; p.res_ldc = Cout;
   Tmp<unsigned long long> tr;
   const Knobs kn = knobs_read();      // (the environment as it is at this call)
   const bool trace = kn.get(K_CONV_TRACE).set;
@@ -218,85 +349,7 @@ int odt_op_conv2d(int device, const float* in, int B, int H, int W, int Cin, con
   if (trace) { if (tr.zero()) return 1; }
   if (run_conv(p, kn)) return 1;
   ODT_HIP(hipDeviceSynchronize());
-  if (trace) {   // tuning aid: per-phase wall-clock (100 MHz) statistics over the workgroups
-    std::vector<unsigned long long> t((size_t)max_blocks * 16);
-    if (tr.get(t.data(), t.size())) return 1;
-    unsigned long long t0 = ~0ull, t1 = 0; int nb = 0;
-    double ph[5] = {0, 0, 0, 0, 0};
-    for (int b = 0; b < max_blocks; ++b) {
-      const unsigned long long* q = &t[(size_t)b * 16];
-      if (q[0] == 0) continue;
-      ++nb; if (q[0] < t0) t0 = q[0]; if (q[5] > t1) t1 = q[5];
-      for (int i = 0; i < 5; ++i) ph[i] += (double)(q[i + 1] - q[i]);
-    }
-    printf("[conv trace] blocks=%d span=%.1f us | per block avg us: prologue %.2f  mainloop %.2f  res-issue+stage0 %.2f  "
-           "pass0 lds->stores %.2f  pass1 %.2f | sum %.2f\n", nb, (t1 - t0) / 100.0, ph[0] / nb / 100, ph[1] / nb / 100,
-           ph[2] / nb / 100, ph[3] / nb / 100, ph[4] / nb / 100, (ph[0] + ph[1] + ph[2] + ph[3] + ph[4]) / nb / 100);
-    // concurrency: how many blocks are in the main loop at the midpoint of the launch
-    const unsigned long long mid = t0 + (t1 - t0) / 2; int in_main = 0, in_epi = 0, in_pro = 0;
-    for (int b = 0; b < max_blocks; ++b) {
-      const unsigned long long* q = &t[(size_t)b * 16];
-      if (q[0] == 0) continue;
-      if (mid >= q[0] && mid < q[1]) ++in_pro; else if (mid >= q[1] && mid < q[2]) ++in_main; else if (mid >= q[2] && mid < q[5]) ++in_epi;
-    }
-    {   // first dispatch wave vs the rest
-      double sa[3] = {0, 0, 0}, sb[3] = {0, 0, 0};
-      double pa = 0, pb = 0, ma = 0, mb = 0; int na = 0, nb2 = 0;
-      for (int b = 0; b < max_blocks; ++b) {
-        const unsigned long long* q = &t[(size_t)b * 16];
-        if (q[0] == 0) continue;
-        double* sx = (q[0] - t0 < 500) ? sa : sb;
-        sx[0] += (double)(q[6] - q[0]); sx[1] += (double)(q[7] - q[6]); sx[2] += (double)(q[1] - q[7]);
-        if (q[0] - t0 < 500) { pa += (double)(q[1] - q[0]); ma += (double)(q[2] - q[1]); ++na; }
-        else { pb += (double)(q[1] - q[0]); mb += (double)(q[2] - q[1]); ++nb2; }
-      }
-      printf("[conv trace] first wave (%d blocks): prologue %.2f us, mainloop %.2f us | later (%d blocks): prologue %.2f us, mainloop %.2f us\n",
-             na, na ? pa / na / 100 : 0.0, na ? ma / na / 100 : 0.0, nb2, nb2 ? pb / nb2 / 100 : 0.0, nb2 ? mb / nb2 / 100 : 0.0);
-      if (na && nb2)
-        printf("[conv trace] prologue split (setup / first loads+lds / barrier): first wave %.2f / %.2f / %.2f us, later %.2f / %.2f / %.2f us\n",
-               sa[0] / na / 100, sa[1] / na / 100, sa[2] / na / 100, sb[0] / nb2 / 100, sb[1] / nb2 / 100, sb[2] / nb2 / 100);
-    }
-    printf("[conv trace] at mid-launch: %d blocks in prologue, %d in main loop, %d in epilogue\n", in_pro, in_main, in_epi);
-    {   // placement and per-CU concurrency: for every CU, the fraction of its busy time with 0 / 1 / 2 / 3+
-        // resident workgroups inside the main loop (lockstep shows up as time with 0 in the loop)
-      std::map<unsigned, std::vector<int>> cu_blocks;
-      for (int b = 0; b < max_blocks; ++b) {
-        const unsigned long long* q = &t[(size_t)b * 16];
-        if (q[0] == 0) continue;
-        const unsigned hw = (unsigned)q[8], xcc = (unsigned)q[9] & 0xf;
-        const unsigned cu = (hw >> 8) & 0xf, sh = (hw >> 12) & 1, se = (hw >> 13) & 0x7;
-        cu_blocks[(xcc << 12) | (se << 8) | (sh << 4) | cu].push_back(b);
-      }
-      double frac[4] = {0, 0, 0, 0}; double busy = 0;
-      for (auto& kv : cu_blocks) {
-        std::vector<std::pair<unsigned long long, int>> ev;   // (time, +1/-1) for main-loop occupancy
-        unsigned long long lo = ~0ull, hi = 0;
-        for (int b : kv.second) {
-          const unsigned long long* q = &t[(size_t)b * 16];
-          ev.push_back({q[1], +1}); ev.push_back({q[2], -1});
-          if (q[0] < lo) lo = q[0]; if (q[5] > hi) hi = q[5];
-        }
-        std::sort(ev.begin(), ev.end());
-        unsigned long long prev = lo; int n = 0;
-        for (auto& e : ev) {
-          frac[n > 3 ? 3 : n] += (double)(e.first - prev); prev = e.first; n += e.second;
-        }
-        frac[0] += (double)(hi - prev); busy += (double)(hi - lo);
-      }
-      printf("[conv trace] %zu CUs seen; time share per CU with k workgroups in the main loop: k=0 %.3f  k=1 %.3f  k=2 %.3f  k>=3 %.3f\n",
-             cu_blocks.size(), frac[0] / busy, frac[1] / busy, frac[2] / busy, frac[3] / busy);
-      // dispatch order on XCD 0: which CU did the first blocks land on
-      printf("[conv trace] XCD0 first blocks -> (se,cu,tg): ");
-      for (int b = 0; b < 8 * 40 && b < max_blocks; b += 8) {
-        const unsigned long long* q = &t[(size_t)b * 16];
-        if (q[0] == 0) break;
-        const unsigned hw = (unsigned)q[8];
-        printf("%u.%u.%u ", (hw >> 13) & 7, (hw >> 8) & 0xf, (hw >> 16) & 0xf);
-      }
-      printf("\n");
-    }
-    fflush(stdout);
-  }
+  if (trace && report_conv_trace(tr, max_blocks)) return 1;
   return dout.get(out, nout);
 }
 
@@ -315,11 +368,7 @@ int odt_op_conv2d_cat(int device, const float* a, int B, int Ho, int Wo, int Ca,
   const size_t na = (size_t)B * Ho * Wo * Ca, nb = (size_t)B * Hb * Wb * Cb, nout = (size_t)B * Ho * Wo * Cout;
   if (da.alloc(na) || db2.alloc(nb) || dw.alloc(w.size()) || dbias.alloc(Cout) || dout.alloc(nout) || dout.zero()) return 1;
   if (da.put(a) || db2.put(b2) || dw.put(w.data()) || dbias.put(bias ? bias : bz.data())) return 1;
-  ConvParams p; std::memset(&p, 0, sizeof(p));
-  p.in = da.d; p.wt = dw.d; p.bias = dbias.d; p.out = dout.d;
-  p.B = B; p.H = Ho; p.W = Wo; p.Cin = Ca; p.in_ldc = Ca; p.in_Ha = Ho; p.in_Wa = Wo;
-  p.Ho = Ho; p.Wo = Wo; p.Cout = Cout; p.kh = 1; p.kw = 1; p.stride = 1; p.dil = 1;
-  p.out_H = Ho; p.out_W = Wo; p.out_ldc = Cout; p.relu = relu;
+  ConvParams p = same_conv(da.d, dw.d, dbias.d, dout.d, B, Ho, Wo, Ca, Cout, 1, 1, relu);
   p.in2 = db2.d; p.Cin2 = Cb; p.in2_ldc = Cb; p.in2_Ha = Hb; p.in2_Wa = Wb; p.in2_stride = stride_b;
   if (run_conv(p, knobs_read())) return 1;
   ODT_HIP(hipDeviceSynchronize());
@@ -336,10 +385,7 @@ int odt_op_bottleneck_tail(int device, const float* in, int B, int H, int W, int
   ODT_CHECK((C == 256 || C == 128 || C == 64) && C3 % 64 == 0 && C3 > 0 && (dil == 1 || dil == 2), "odt_op_bottleneck_tail: C = 64 / 128 / 256, C3 % 64 == 0, dil 1 or 2");
   if (set_dev(device)) return 1;
   const size_t M = (size_t)B * H * W;
-  std::vector<float> w2((size_t)C * 9 * C), w3((size_t)C3 * C);
-  for (int y = 0; y < 3; ++y) for (int x = 0; x < 3; ++x) for (int i = 0; i < C; ++i) for (int o = 0; o < C; ++o)
-    w2[(((size_t)o * 3 + y) * 3 + x) * C + i] = w2_hwio[(((size_t)y * 3 + x) * C + i) * C + o];
-  for (int i = 0; i < C; ++i) for (int o = 0; o < C3; ++o) w3[(size_t)o * C + i] = w3_io[(size_t)i * C3 + o];
+  const std::vector<float> w2 = ohwi(w2_hwio, 3, 3, C, C), w3 = ohwi(w3_io, 1, 1, C, C3);
   Tmp<float> di, dw2, db2, dw3, db3, dres, dmid, dout, img2, img3, imgf;
   Tmp<unsigned> amax;
   if (di.alloc(M * C) || dw2.alloc(w2.size()) || db2.alloc(C) || dw3.alloc(w3.size()) || db3.alloc(C3) || dmid.alloc(M * C) ||
@@ -347,36 +393,19 @@ int odt_op_bottleneck_tail(int device, const float* in, int B, int H, int W, int
   if (di.put(in) || dw2.put(w2.data()) || db2.put(b2) || dw3.put(w3.data()) || db3.put(b3)) return 1;
   if (res) { if (dres.alloc(M * C3) || dres.put(res)) return 1; }
   if (launch_tensor_amax(di.d, M * C, amax.d, nullptr)) return 1;
-  ConvParams a; std::memset(&a, 0, sizeof(a));
-  a.in = di.d; a.wt = dw2.d; a.bias = db2.d; a.out = dmid.d;
-  a.B = B; a.H = H; a.W = W; a.Cin = C; a.in_ldc = C; a.in_Ha = H; a.in_Wa = W; a.Ho = H; a.Wo = W; a.Cout = C;
-  a.kh = 3; a.kw = 3; a.stride = 1; a.dil = dil; a.pad_t = dil; a.pad_l = dil;
-  a.out_H = H; a.out_W = W; a.out_ldc = C; a.relu = 1;
-  conv_use_variant(a, conv_variant_find(CF_H2, 256, C, CVF_KWR));
-  a.in_amax = amax.d; a.out_amax = amax.d + kAmaxWays; a.debug = 0x400;
-  conv_prepare(a);
-  if (img2.alloc((conv_split_weight_bytes(C, 9 * C) + 3) / 4) || conv_make_split_weights(a, img2.d, nullptr)) return 1;
-  a.wt_split = img2.d; a.h2_chinv = conv_h2_chinv(img2.d, C, 9 * C);
-  ConvParams b; std::memset(&b, 0, sizeof(b));
-  b.in = dmid.d; b.wt = dw3.d; b.bias = db3.d; b.out = dout.d; b.res = res ? dres.d : nullptr;
-  b.B = B; b.H = H; b.W = W; b.Cin = C; b.in_ldc = C; b.in_Ha = H; b.in_Wa = W; b.Ho = H; b.Wo = W; b.Cout = C3;
-  b.kh = 1; b.kw = 1; b.stride = 1; b.dil = 1;
-  b.out_H = H; b.out_W = W; b.out_ldc = C3; b.relu = relu3 ? 1 : 0;
-  b.res_mode = res ? 1 : 0; b.res_H = H; b.res_W = W; b.res_ldc = C3;
-  conv_use_variant(b, C3 % 256 == 0 ? CV_H2_256x256 : (C3 % 128 == 0 ? CV_H2_256x128 : CV_H2_128x64));
-  b.in_amax = amax.d + kAmaxWays; b.out_amax = amax.d + 2 * kAmaxWays; b.debug = 0x400;
-  conv_prepare(b);
-  if (img3.alloc((conv_split_weight_bytes(C3, C) + 3) / 4) || conv_make_split_weights(b, img3.d, nullptr)) return 1;
-  b.wt_split = img3.d; b.h2_chinv = conv_h2_chinv(img3.d, C3, C);
+  unsigned* const slot[3] = {amax.d, amax.d + kAmaxWays, amax.d + 2 * kAmaxWays};      // ranges of in, conv2's and conv3's output
+  ConvParams a = same_conv(di.d, dw2.d, db2.d, dmid.d, B, H, W, C, C, 3, dil, 1);
+  a.debug = 0x400;
+  if (use_h2_row(a, conv_variant_find(CF_H2, 256, C, CVF_KWR), slot[0], slot[1], img2)) return 1;
+  ConvParams b = same_conv(dmid.d, dw3.d, db3.d, dout.d, B, H, W, C, C3, 1, 1, relu3 ? 1 : 0);
+  b.res = res ? dres.d : nullptr; b.res_mode = res ? 1 : 0; b.res_H = H; b.res_W = W; b.res_ldc = C3; b.debug = 0x400;
+  if (use_h2_row(b, C3 % 256 == 0 ? CV_H2_256x256 : (C3 % 128 == 0 ? CV_H2_256x128 : CV_H2_128x64), slot[1], slot[2], img3)) return 1;
   Tmp<ConvParams> rec;
   if (rec.alloc(2)) return 1;
   if (fuse) {
     ODT_CHECK(conv_h2f_fusable(a, b), "odt_op_bottleneck_tail: this pair is not fusable");
-    conv_use_variant(a, conv_variant_fused_tail(a.variant));
     if (imgf.alloc((conv_h2f_weight_bytes(C3, C) + 3) / 4) || conv_make_h2f_weights(dw3.d, C3, C, imgf.d, nullptr)) return 1;
-    a.f_wt = imgf.d; a.f_chinv = conv_h2f_chinv(imgf.d, C3, C); a.f_bias = db3.d; a.f_res = b.res; a.f_res_ldc = C3;
-    a.f_out = dout.d; a.f_out_ldc = C3; a.f_cout = C3; a.f_relu = b.relu; a.f_out_amax = amax.d + 2 * kAmaxWays;
-    a.out = nullptr; a.out_amax = nullptr;
+    conv_h2f_fuse(a, b, imgf.d);
     ConvParams recs[2] = {a, b};
     if (conv_check(a) || rec.put(recs)) return 1;
     note_conv(a);
@@ -401,61 +430,31 @@ int odt_op_bottleneck_block(int device, const float* x, int B, int H, int W, int
   if (set_dev(device)) return 1;
   const int C4 = 4 * C;
   const size_t M = (size_t)B * H * W;
-  std::vector<float> w1((size_t)C * C4), w2((size_t)C * 9 * C), w3((size_t)C4 * C);
-  for (int i = 0; i < C4; ++i) for (int o = 0; o < C; ++o) w1[(size_t)o * C4 + i] = w1_io[(size_t)i * C + o];
-  for (int y = 0; y < 3; ++y) for (int xx = 0; xx < 3; ++xx) for (int i = 0; i < C; ++i) for (int o = 0; o < C; ++o)
-    w2[(((size_t)o * 3 + y) * 3 + xx) * C + i] = w2_hwio[(((size_t)y * 3 + xx) * C + i) * C + o];
-  for (int i = 0; i < C; ++i) for (int o = 0; o < C4; ++o) w3[(size_t)o * C + i] = w3_io[(size_t)i * C4 + o];
+  const std::vector<float> w1 = ohwi(w1_io, 1, 1, C4, C), w2 = ohwi(w2_hwio, 3, 3, C, C), w3 = ohwi(w3_io, 1, 1, C, C4);
   Tmp<float> dx, dw1, db1, dw2, db2, dw3, db3, dt1, dt2, dout, img1, img2, img2p, img3, imgf;
   Tmp<unsigned> amax;
   if (dx.alloc(M * C4) || dw1.alloc(w1.size()) || db1.alloc(C) || dw2.alloc(w2.size()) || db2.alloc(C) || dw3.alloc(w3.size()) ||
       db3.alloc(C4) || dt1.alloc(M * C) || dt2.alloc(M * C) || dout.alloc(M * C4) || dout.zero() || amax.alloc(4 * kAmaxWays) || amax.zero()) return 1;
   if (dx.put(x) || dw1.put(w1.data()) || db1.put(b1) || dw2.put(w2.data()) || db2.put(b2) || dw3.put(w3.data()) || db3.put(b3)) return 1;
   if (launch_tensor_amax(dx.d, M * C4, amax.d, nullptr)) return 1;
-  ConvParams c1; std::memset(&c1, 0, sizeof(c1));
-  c1.in = dx.d; c1.wt = dw1.d; c1.bias = db1.d; c1.out = dt1.d;
-  c1.B = B; c1.H = H; c1.W = W; c1.Cin = C4; c1.in_ldc = C4; c1.in_Ha = H; c1.in_Wa = W; c1.Ho = H; c1.Wo = W; c1.Cout = C;
-  c1.kh = 1; c1.kw = 1; c1.stride = 1; c1.dil = 1; c1.out_H = H; c1.out_W = W; c1.out_ldc = C; c1.relu = 1;
-  conv_use_variant(c1, CV_H2_128x64);
-  c1.in_amax = amax.d; c1.out_amax = amax.d + kAmaxWays;
-  conv_prepare(c1);
-  if (img1.alloc((conv_split_weight_bytes(C, C4) + 3) / 4) || conv_make_split_weights(c1, img1.d, nullptr)) return 1;
-  c1.wt_split = img1.d; c1.h2_chinv = conv_h2_chinv(img1.d, C, C4);
-  ConvParams a; std::memset(&a, 0, sizeof(a));
-  a.in = dt1.d; a.wt = dw2.d; a.bias = db2.d; a.out = dt2.d;
-  a.B = B; a.H = H; a.W = W; a.Cin = C; a.in_ldc = C; a.in_Ha = H; a.in_Wa = W; a.Ho = H; a.Wo = W; a.Cout = C;
-  a.kh = 3; a.kw = 3; a.stride = 1; a.dil = 1; a.pad_t = 1; a.pad_l = 1;
-  a.out_H = H; a.out_W = W; a.out_ldc = C; a.relu = 1;
-  conv_use_variant(a, conv_variant_find(CF_H2, 256, C, CVF_KWR));
-  a.in_amax = amax.d + kAmaxWays; a.out_amax = amax.d + 2 * kAmaxWays; a.debug = 0x400;
-  conv_prepare(a);
-  if (img2.alloc((conv_split_weight_bytes(C, 9 * C) + 3) / 4) || conv_make_split_weights(a, img2.d, nullptr)) return 1;
-  a.wt_split = img2.d; a.h2_chinv = conv_h2_chinv(img2.d, C, 9 * C);
-  ConvParams b; std::memset(&b, 0, sizeof(b));
-  b.in = dt2.d; b.wt = dw3.d; b.bias = db3.d; b.out = dout.d; b.res = dx.d;
-  b.B = B; b.H = H; b.W = W; b.Cin = C; b.in_ldc = C; b.in_Ha = H; b.in_Wa = W; b.Ho = H; b.Wo = W; b.Cout = C4;
-  b.kh = 1; b.kw = 1; b.stride = 1; b.dil = 1;
-  b.out_H = H; b.out_W = W; b.out_ldc = C4; b.relu = 1;
-  b.res_mode = 1; b.res_H = H; b.res_W = W; b.res_ldc = C4;
-  conv_use_variant(b, CV_H2_256x256);
-  b.in_amax = amax.d + 2 * kAmaxWays; b.out_amax = amax.d + 3 * kAmaxWays; b.debug = 0x400;
-  conv_prepare(b);
-  if (img3.alloc((conv_split_weight_bytes(C4, C) + 3) / 4) || conv_make_split_weights(b, img3.d, nullptr)) return 1;
-  b.wt_split = img3.d; b.h2_chinv = conv_h2_chinv(img3.d, C4, C);
+  unsigned* const slot[4] = {amax.d, amax.d + kAmaxWays, amax.d + 2 * kAmaxWays, amax.d + 3 * kAmaxWays};      // ranges of x, t1, t2, out
+  ConvParams c1 = same_conv(dx.d, dw1.d, db1.d, dt1.d, B, H, W, C4, C, 1, 1, 1);
+  if (use_h2_row(c1, CV_H2_128x64, slot[0], slot[1], img1)) return 1;
+  ConvParams a = same_conv(dt1.d, dw2.d, db2.d, dt2.d, B, H, W, C, C, 3, 1, 1);
+  a.debug = 0x400;
+  if (use_h2_row(a, conv_variant_find(CF_H2, 256, C, CVF_KWR), slot[1], slot[2], img2)) return 1;
+  ConvParams b = same_conv(dt2.d, dw3.d, db3.d, dout.d, B, H, W, C, C4, 1, 1, 1);
+  b.res = dx.d; b.res_mode = 1; b.res_H = H; b.res_W = W; b.res_ldc = C4; b.debug = 0x400;
+  if (use_h2_row(b, CV_H2_256x256, slot[2], slot[3], img3)) return 1;
   Tmp<ConvParams> rec;
   if (rec.alloc(3)) return 1;
   if (fuse) {
     ODT_CHECK(conv_h2f_fusable(a, b), "odt_op_bottleneck_block: conv2 + conv3 are not fusable");
-    conv_use_variant(a, conv_variant_fused_tail(a.variant));
     if (imgf.alloc((conv_h2f_weight_bytes(C4, C) + 3) / 4) || conv_make_h2f_weights(dw3.d, C4, C, imgf.d, nullptr)) return 1;
-    a.f_wt = imgf.d; a.f_chinv = conv_h2f_chinv(imgf.d, C4, C); a.f_bias = db3.d; a.f_res = dx.d; a.f_res_ldc = C4;
-    a.f_out = dout.d; a.f_out_ldc = C4; a.f_cout = C4; a.f_relu = 1; a.f_out_amax = amax.d + 3 * kAmaxWays;
-    a.out = nullptr; a.out_amax = nullptr;
+    conv_h2f_fuse(a, b, imgf.d);
     ODT_CHECK(conv_block_fits(c1, a), "odt_op_bottleneck_block: this block does not fit conv_block_kernel");
     if (img2p.alloc((conv_split_weight_bytes(C, 9 * C) + 3) / 4) || conv_make_h2p_weights(a, img2p.d, nullptr)) return 1;
-    a.b_in = dx.d; a.b_in_ldc = C4; a.b_cin = C4; a.b_wt = c1.wt_split; a.b_chinv = c1.h2_chinv; a.b_bias = c1.bias;
-    a.b_in_amax = c1.in_amax; a.b_wt2 = img2p.d;
-    a.in = dx.d; a.in_amax = c1.in_amax;      // (t1 does not exist)
+    conv_block_fuse(a, c1, img2p.d);      // (t1 does not exist)
     // ODT_CONV_TRACE (tuning): per-phase wall-clock (100 MHz) averages over the workgroups
     const bool trace = knobs_read().get(K_CONV_TRACE).set;
     const size_t ntile = (size_t)B * ((H + 15) / 16) * ((W + 15) / 16);
@@ -465,22 +464,7 @@ int odt_op_bottleneck_block(int device, const float* x, int B, int H, int W, int
     if (conv_check(a) || rec.put(recs)) return 1;
     note_conv(a);
     if (launch_bottleneck_block(a, rec.d, nullptr)) return 1;
-    if (trace) {
-      ODT_HIP(hipDeviceSynchronize());
-      std::vector<unsigned long long> t(ntile * 16);
-      if (tr.get(t.data(), t.size())) return 1;
-      double ph[5] = {0, 0, 0, 0, 0};
-      unsigned long long t0 = ~0ull, t1 = 0;
-      for (size_t i = 0; i < ntile; ++i) {
-        const unsigned long long* q = &t[i * 16];
-        ph[0] += (double)(q[1] - q[0]); ph[1] += (double)(q[2] - q[1]); ph[2] += (double)(q[6] - q[2]); ph[3] += (double)(q[3] - q[6]); ph[4] += (double)(q[5] - q[3]);
-        if (q[0] < t0) t0 = q[0];
-        if (q[5] > t1) t1 = q[5];
-      }
-      printf("[block trace] tiles=%zu span=%.1f us | per tile avg us: conv1 loop %.2f  patch %.2f  conv2 %.2f  tail pieces %.2f  conv3 + stores %.2f\n",
-             ntile, (t1 - t0) / 100.0, ph[0] / ntile / 100, ph[1] / ntile / 100, ph[2] / ntile / 100, ph[3] / ntile / 100, ph[4] / ntile / 100);
-      fflush(stdout);
-    }
+    if (trace && report_block_trace(tr, ntile)) return 1;
   } else {
     ConvParams recs[3] = {c1, a, b};
     if (conv_check(c1) || conv_check(a) || conv_check(b) || rec.put(recs)) return 1;
@@ -512,18 +496,12 @@ int odt_op_stem(int device, const float* frame_pad, int B, int Hp, int Wp, const
       amax.alloc(4 * kAmaxWays) || amax.zero() || rec.alloc(1)) return 1;
   if (di.put(x.data()) || dw.put(wv.data()) || db.put(bias)) return 1;
   if (launch_tensor_amax(di.d, x.size(), amax.d, nullptr)) return 1;
-  ConvParams p; std::memset(&p, 0, sizeof(p));
-  p.in = di.d; p.wt = dw.d; p.bias = db.d; p.out = dmap.d;
-  p.B = B; p.H = Hp; p.W = Wa; p.Cin = 32; p.in_ldc = 4; p.in_Ha = Hp; p.in_Wa = Wa; p.Ho = Ho0; p.Wo = Wo0; p.Cout = 64;
-  p.kh = 7; p.kw = 1; p.stride = 2; p.dil = 1; p.out_H = Ho0; p.out_W = Wo0; p.out_ldc = 64; p.relu = 1;
-  conv_use_variant(p, CV_H2_128x64);
-  p.in_amax = amax.d; p.out_amax = amax.d + kAmaxWays;
-  conv_prepare(p);
-  if (img.alloc((conv_split_weight_bytes(64, 224) + 3) / 4) || conv_make_split_weights(p, img.d, nullptr)) return 1;
-  p.wt_split = img.d; p.h2_chinv = conv_h2_chinv(img.d, 64, 224);
+  ConvParams p = dense_conv(di.d, dw.d, db.d, dmap.d, B, Hp, Wa, 32, Ho0, Wo0, 64, 7, 1, 2, 1, 0, 0, 1);
+  p.in_ldc = 4;      // (Cin = 32: eight 4-channel pixels)
+  if (use_h2_row(p, CV_H2_128x64, amax.d, amax.d + kAmaxWays, img)) return 1;
   if (fuse) {
     ODT_CHECK(conv_stem_fits(p), "odt_op_stem: shape not taken by the stem kernel");
-    p.out = dout.d; p.out_H = Hq; p.out_W = Wq; conv_use_variant(p, CV_H2_STEM);
+    conv_stem_fuse(p, dout.d, Hq, Wq, p.out_ldc);
     if (grid > 0) p.debug |= (grid & 0x3ff) << 20;
     if (conv_check(p) || rec.put(&p)) return 1;
     note_conv(p);
@@ -547,12 +525,10 @@ int odt_op_conv_choice(const int* shape, int conv_arith, int conv_split_family, 
   for (int i = 0; i < ODT_CONV_CHOICE_OUT; ++i) out[i] = 0;
   if (name && name_cap > 0) name[0] = 0;
   const int* s = shape;
-  ConvParams q; std::memset(&q, 0, sizeof(q));
-  q.in = ph_f; q.wt = ph_f; q.bias = ph_f; q.out = ph_f;
-  q.B = s[0]; q.H = s[1]; q.W = s[2]; q.Cin = s[3]; q.Cout = s[4]; q.kh = s[5]; q.kw = s[6]; q.stride = s[7]; q.dil = s[8];
-  q.pad_t = s[9]; q.pad_l = s[9]; q.Ho = s[10]; q.Wo = s[11]; q.in_Wa = s[12]; q.in_Ha = q.H;
-  q.in_ldc = s[16] > 0 ? s[16] : q.Cin; q.out_ldc = s[17] > 0 ? s[17] : q.Cout;
-  q.out_H = q.Ho; q.out_W = q.Wo;
+  ConvParams q = dense_conv(ph_f, ph_f, ph_f, ph_f, s[0], s[1], s[2], s[3], s[10], s[11], s[4], s[5], s[6], s[7], s[8], s[9], s[9], 0);
+  q.in_Wa = s[12];
+  if (s[16] > 0) q.in_ldc = s[16];
+  if (s[17] > 0) q.out_ldc = s[17];
   if (s[13] > 0) { q.in2 = ph_f; q.Cin2 = s[13]; q.in2_ldc = s[13]; q.in2_Ha = q.Ho; q.in2_Wa = q.Wo; q.in2_stride = 1; }
   q.res_mode = s[14];
   if (q.res_mode != 0) {
@@ -1035,8 +1011,7 @@ int odt_op_se_tail(int device, const float* t2, int B, int H, int W, int ch, con
   if (set_dev(device)) return 1;
   const int C3 = ch * 4, r = ch / 4, HW = H * W;
   const size_t M = (size_t)B * HW;
-  std::vector<float> w3t((size_t)C3 * ch);
-  for (int i = 0; i < ch; ++i) for (int o = 0; o < C3; ++o) w3t[(size_t)o * ch + i] = w3[(size_t)i * C3 + o];
+  const std::vector<float> w3t = ohwi(w3, 1, 1, ch, C3);
   GBufs g;
   ResSeParams gp;
   float *dt2, *dw3, *db3, *ds, *dy, *dout;
@@ -1047,11 +1022,7 @@ int odt_op_se_tail(int device, const float* t2, int B, int H, int W, int ch, con
   gp.t2 = dt2;
   // the plan's order: pool + gate, conv3 (BN folded, no residual, no ReLU), apply
   if (launch_resnet_se_gate(gp, nullptr)) return 1;
-  ConvParams p; std::memset(&p, 0, sizeof(p));
-  p.in = dt2; p.wt = dw3; p.bias = db3; p.out = dy;
-  p.B = B; p.H = H; p.W = W; p.Cin = ch; p.in_ldc = ch; p.in_Ha = H; p.in_Wa = W; p.Ho = H; p.Wo = W; p.Cout = C3;
-  p.kh = 1; p.kw = 1; p.stride = 1; p.dil = 1; p.out_H = H; p.out_W = W; p.out_ldc = C3;
-  if (run_conv(p, knobs_read())) return 1;
+  if (run_conv(same_conv(dt2, dw3, db3, dy, B, H, W, ch, C3, 1, 1, 0), knobs_read())) return 1;
   ResSeApplyParams ap; std::memset(&ap, 0, sizeof(ap));
   ap.y = dy; ap.sc = ds; ap.gate = gp.gate; ap.out = dout; ap.amax = slot;
   ap.B = B; ap.HW = HW; ap.C = C3; ap.ldc = C3; ap.gate_ld = gp.gate_ld;

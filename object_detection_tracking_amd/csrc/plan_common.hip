@@ -369,16 +369,15 @@ int attach_split_weights(odt_model* m) {
     const ConvKernelRow& row = conv_variant_row(ch.variant);
     if (row.family == CF_F32) { slot_of.erase(c.p.out); continue; }      // exact-f32 kernel (conv_finish picks its row): records no range
     conv_use_variant(c.p, ch.variant, ch.splitk, ch.reduce_blocks);
-    const int K = c.p.kh * c.p.kw * c.p.Cin + (c.p.in2 != nullptr ? c.p.Cin2 : 0);
     const auto key = std::make_pair(c.p.wt, row.family * 1024 + row.bn);      // (the weight image's layout)
     auto it = made.find(key);
     if (it == made.end()) {
-      float* img = m->alloc_f((conv_split_weight_bytes(c.p.Cout, K) + 3) / 4, false);
+      float* img = m->alloc_f((conv_split_weight_bytes(c.p.Cout, conv_k(c.p)) + 3) / 4, false);
       ODT_CHECK(img != nullptr, "device allocation failed (split weights of " + c.name + ")");
       if (conv_make_split_weights(c.p, img, 0)) return 1;
       it = made.emplace(key, img).first;
     }
-    c.p.wt_split = it->second;
+    conv_attach_weights(c.p, it->second);
     {
       // non-temporal hints on the loads of data that one workgroup reads once -- residual chunks (1), the activations of a 1x1
       // layer with a single n-tile (2) -- keep them from pushing the weights and the re-read tensors out of L2 / MALL: same-box
@@ -393,7 +392,7 @@ int attach_split_weights(odt_model* m) {
       if (per_wave) c.p.debug |= 0x4000;      // A/B: range record per wave instead of per workgroup
     }
     if (row.family == CF_H2) {
-      c.p.h2_chinv = conv_h2_chinv(c.p.wt_split, c.p.Cout, K); ++m->convs_h2;
+      ++m->convs_h2;
       const bool norot = m->knobs.off(K_CONV_H2_ROT);
       if (norot) c.p.debug |= 0x100;          // A/B: every workgroup walks the K slices in the same order
     }
@@ -483,6 +482,17 @@ int fuse_rpn_heads(odt_model* m) {
   return 0;
 }
 
+// does anything but ops a and b -- another op, or (taps) a tap -- name tensor t?  What a fusion asks before it drops t.
+static bool used_elsewhere(odt_model* m, const void* t, size_t a, size_t b, bool taps) {
+  bool other = false;
+  for (size_t k = 0; k < m->ops.size() && !other; ++k) {
+    if (k == a || k == b) continue;
+    visit_op_ptrs(m, k, [&](auto& ptr) { if ((const void*)ptr == t) other = true; });
+  }
+  if (taps) for (const auto& kv : m->taps) if (kv.second.d == t) other = true;
+  return other;
+}
+
 // ---- bottleneck tail folded into the 3x3 conv's kernel ----------------------------------------------------------------
 // block/conv2 (3x3, ch -> ch, BN, ReLU) is read by block/conv3 (1x1, ch -> 4 ch, BN, + shortcut, ReLU) and by nothing else
 // (nn.py:503-521).  Where conv2 runs on conv_h2k_kernel with its whole Cout in one 256-wide n-tile (res4 at b >= 4 @1080p)
@@ -509,29 +519,16 @@ int fuse_bottleneck_tails(odt_model* m) {
     if (a.p.Cout < min_cout) continue;
     if (!conv_h2f_fusable(a.p, b.p)) continue;
     // nothing else may read conv2's output (taps: a keep_taps handle exposes no stage tensor under this name, see add_conv)
-    bool other = false;
-    for (size_t k = 0; k < m->ops.size() && !other; ++k) {
-      if (k == oi || k == oi + 1) continue;
-      visit_op_ptrs(m, k, [&](auto& ptr) { if ((const void*)ptr == (const void*)a.p.out) other = true; });
-    }
-    for (const auto& kv : m->taps) if (kv.second.d == a.p.out) other = true;
-    if (other) continue;
-    const int K = b.p.Cin;
+    if (used_elsewhere(m, a.p.out, oi, oi + 1, true)) continue;
     auto it = made.find(b.p.wt);
     if (it == made.end()) {
-      float* img = m->alloc_f((conv_h2f_weight_bytes(b.p.Cout, K) + 3) / 4, false);
+      float* img = m->alloc_f((conv_h2f_weight_bytes(b.p.Cout, b.p.Cin) + 3) / 4, false);
       ODT_CHECK(img != nullptr, "device allocation failed (fused 1x1 weights of " + b.name + ")");
-      if (conv_make_h2f_weights(b.p.wt, b.p.Cout, K, img, 0)) return 1;
+      if (conv_make_h2f_weights(b.p.wt, b.p.Cout, b.p.Cin, img, 0)) return 1;
       it = made.emplace(b.p.wt, img).first;
     }
-    ConvParams& ap = a.p;
-    conv_use_variant(ap, conv_variant_fused_tail(ap.variant), ap.splitk, ap.reduce_blocks);
-    ap.f_wt = it->second; ap.f_chinv = conv_h2f_chinv(it->second, b.p.Cout, K); ap.f_bias = b.p.bias;
-    ap.f_res = b.p.res_mode != 0 ? b.p.res : nullptr; ap.f_res_ldc = b.p.res_ldc;
-    ap.f_out = b.p.out; ap.f_out_ldc = b.p.out_ldc; ap.f_cout = b.p.Cout; ap.f_relu = b.p.relu; ap.f_out_amax = b.p.out_amax;
-    ap.debug |= b.p.debug & 0x400;           // the residual's non-temporal hint travels with it
-    if (m->knobs.off(K_FUSE_ROT)) ap.debug |= 0x100;     // A/B: 0 = every workgroup walks the output column chunks in the same order
-    ap.out = nullptr; ap.out_amax = nullptr;
+    conv_h2f_fuse(a.p, b.p, it->second);
+    if (m->knobs.off(K_FUSE_ROT)) a.p.debug |= 0x100;     // A/B: 0 = every workgroup walks the output column chunks in the same order
     ob.skip = true;
     m->conv_fused[ob.conv] = 2;
     ++m->convs_h2f;
@@ -564,13 +561,7 @@ int fuse_bottleneck_blocks(odt_model* m) {
     ConvOp& c1 = m->convs[o1.conv]; ConvOp& c2 = m->convs[o2.conv];
     if (c2.p.variant != CV_H2KF_256x64 || c2.p.f_out != m->convs[o3.conv].p.out || !conv_block_fits(c1.p, c2.p)) continue;
     // nothing else may read conv1's output
-    bool other = false;
-    for (size_t k = 0; k < m->ops.size() && !other; ++k) {
-      if (k == oi || k == oi + 1) continue;
-      visit_op_ptrs(m, k, [&](auto& ptr) { if ((const void*)ptr == (const void*)c1.p.out) other = true; });
-    }
-    for (const auto& kv : m->taps) if (kv.second.d == c1.p.out) other = true;
-    if (other) continue;
+    if (used_elsewhere(m, c1.p.out, oi, oi + 1, true)) continue;
     ConvParams q = c2.p;
     q.in = c1.p.in; q.in_ldc = c1.p.in_ldc;
     if (conv_batch_chunks(q, limit) != 1 || conv_batch_chunks(c1.p, limit) != 1) continue;
@@ -581,12 +572,8 @@ int fuse_bottleneck_blocks(odt_model* m) {
       if (conv_make_h2p_weights(c2.p, img, 0)) return 1;
       it = made.emplace(c2.p.wt, img).first;
     }
-    ConvParams& p = c2.p;
-    p.b_in = c1.p.in; p.b_in_ldc = c1.p.in_ldc; p.b_cin = c1.p.Cin; p.b_wt = c1.p.wt_split; p.b_chinv = c1.p.h2_chinv;
-    p.b_bias = c1.p.bias; p.b_in_amax = c1.p.in_amax; p.b_wt2 = it->second;
-    p.in = c1.p.in; p.in_amax = c1.p.in_amax;        // (conv1's output does not exist: the record names real memory only)
-    if ((c1.p.debug & 0x100) != 0) p.debug |= 0x100;
-    if (m->knobs.get(K_FUSE_BLOCK).c0 == '2') p.debug |= 0x200;      // A/B: no first-round stagger
+    conv_block_fuse(c2.p, c1.p, it->second);
+    if (m->knobs.get(K_FUSE_BLOCK).c0 == '2') c2.p.debug |= 0x200;      // A/B: no first-round stagger
     o1.skip = true;
     m->conv_fused[o1.conv] = 3;
     o2.kind = OP_BLOCK;
@@ -611,18 +598,12 @@ int fuse_stem(odt_model* m) {
     if (ob.in.d != ap.out || ap.out == nullptr || !conv_stem_fits(ap) || ap.out_oy != 0 || ap.out_ox != 0 || ap.out_H != ap.Ho || ap.out_W != ap.Wo ||
         ob.in.h != ap.Ho || ob.in.w != ap.Wo || ob.in.C != 64 || ob.out.H != (ap.Ho + 1 - 3) / 2 + 1 || ob.out.W != (ap.Wo + 1 - 3) / 2 + 1 ||
         ob.out.C < 64 || (double)ap.B * ob.out.H * ob.out.W * ob.out.C * 4.0 >= 2147483648.0) continue;
-    bool other = false;                      // nothing else may read the conv map (a keep_taps handle exposes it as "conv0")
-    for (size_t k = 0; k < m->ops.size() && !other; ++k) {
-      if (k == oi || k == oi + 1) continue;
-      visit_op_ptrs(m, k, [&](auto& ptr) { if ((const void*)ptr == (const void*)ap.out) other = true; });
-    }
-    // (arena handles keep no stage tensor: odt_tap refuses the transient ones)
-    if (!m->arena_on) for (const auto& kv : m->taps) if (kv.second.d == ap.out) other = true;
-    if (other) continue;
+    // nothing else may read the conv map (a keep_taps handle exposes it as "conv0"; arena handles keep no stage tensor: odt_tap
+    // refuses the transient ones)
+    if (used_elsewhere(m, ap.out, oi, oi + 1, !m->arena_on)) continue;
     // the conv map no longer exists: an arena handle must neither reserve memory for its stage name nor hand it out
     for (auto it = m->taps.begin(); it != m->taps.end();) { if (it->second.d == ap.out) it = m->taps.erase(it); else ++it; }
-    ap.out = ob.out.d; ap.out_H = ob.out.H; ap.out_W = ob.out.W; ap.out_ldc = ob.out.C;
-    conv_use_variant(ap, CV_H2_STEM, ap.splitk, ap.reduce_blocks);
+    conv_stem_fuse(ap, ob.out.d, ob.out.H, ob.out.W, ob.out.C);
     if (m->knobs.get(K_STEM_GRID).set) ap.debug |= ((int)m->knobs.get(K_STEM_GRID).i & 0x3ff) << 20;   // test knob: workgroups of the launch
     ob.skip = true;
     m->stem_fused = 1;
