@@ -223,6 +223,9 @@ namespace odt {
 int ceil_div(int a, int b);
 int make_tensor(odt_model* m, const std::string& name, int B, int H, int W, int C, Tensor* t, bool zero = false);
 const HostTensor* find_w(odt_model* m, const std::string& name);
+int same_pad(int in, int k, int s, int* out, int* before);
+int bn_fold(odt_model* m, const std::string& scope, int c, double eps, bool keras, std::vector<double>* scale,
+            std::vector<double>* shift);
 int upload_conv(odt_model* m, const std::string& scope, int kh, int kw, int cin, int cout, bool has_bn, const float** wt_out,
                 const float** bias_out);
 int upload_conv_cat(odt_model* m, const std::string& sa, int cin_a, const std::string& sb, int cin_b, int cout,
@@ -232,9 +235,26 @@ int upload_group_conv(odt_model* m, const std::string& scope, int C, const float
 int upload_deform_conv(odt_model* m, const std::string& pre, int C, const float** wt_off, const float** b_off, const float** wt);
 int upload_se_gate(odt_model* m, const std::string& pre, int ch, const float** w1, const float** b1, const float** w2t,
                    const float** b2);
-int add_conv(odt_model* m, const std::string& name, const Tensor& in, int cin, const float* wt, const float* bias, int kh,
-             int kw, int cout, int stride, int dil, int pad_t, int pad_l, int Ho, int Wo, int oy, int ox, const Tensor* res,
-             int res_mode, bool relu, int out_ldc, Tensor* out, const std::string& tap);
+// One conv layer of a plan.  What the constructor does not take defaults to a dense same-size conv: 1x1, stride 1, no padding,
+// an output of the input's logical size at offset 0 with Cout as its pixel stride, no residual, no activation, no tap.
+struct ConvSpec {
+  std::string name;
+  Tensor in;                          // its logical dims (h, w) bound the reads
+  int cin, cout;
+  const float *wt = nullptr, *bias = nullptr;   // [cout][kh][kw][cin], [cout] on the device
+  int kh = 1, kw = 1, stride = 1, dil = 1, pad_t = 0, pad_l = 0;
+  int Ho = -1, Wo = -1;               // -1: in.h / in.w
+  int oy = 0, ox = 0;                 // the output's offset in a tensor of [Ho + oy, Wo + ox] pixels
+  const Tensor* res = nullptr;        // residual, added as res_mode says (ConvParams::res_mode)
+  int res_mode = 0;
+  int relu = 0;                       // ConvParams::relu: 0 none | 1 ReLU | 2 swish | 3 sigmoid
+  int out_ldc = -1;                   // -1: cout
+  const Tensor* in2 = nullptr;        // second source, K-concatenated behind the first: its first cin2 channels at every
+  int cin2 = 0, in2_stride = 1;       // in2_stride-th pixel
+  std::string tap;                    // stage name of the output
+  ConvSpec(const std::string& name_, const Tensor& in_, int cin_, int cout_) : name(name_), in(in_), cin(cin_), cout(cout_) {}
+};
+int add_conv(odt_model* m, const ConvSpec& s, Tensor* out);
 int create_side_stream(hipStream_t* s, const Knobs& k);
 ConvPolicy resolve_conv_policy(const odt_model* m);
 int attach_split_weights(odt_model* m);

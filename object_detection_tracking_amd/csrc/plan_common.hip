@@ -35,6 +35,36 @@ const HostTensor* find_w(odt_model* m, const std::string& name) {
   return it == m->host_w.end() ? nullptr : &it->second;
 }
 
+// TensorFlow's 'SAME' geometry (conv2d's default padding, nn.py:337-381): out = ceil(in / s), the smaller half of the padding
+// in front.  The rest lies behind the input, where the kernels read zeros anyway.  Returns the padding of both sides together.
+int same_pad(int in, int k, int s, int* out, int* before) {
+  *out = (in + s - 1) / s;
+  const int tot = std::max((*out - 1) * s + k - in, 0);
+  *before = tot / 2;
+  return tot;
+}
+
+// BN fold factors of the c channels of `scope`, in double: tf.nn.batch_normalization (nn.py:1771-1774).  The detector's
+// variables are bn/gamma, bn/beta, bn/mean/EMA, bn/variance/EMA (eps 1e-5); a Keras BatchNormalization scope (keras) holds
+// gamma, beta, moving_mean, moving_variance (EfficientDet: eps 1e-3).
+int bn_fold(odt_model* m, const std::string& scope, int c, double eps, bool keras, std::vector<double>* scale,
+            std::vector<double>* shift) {
+  const HostTensor* g = find_w(m, scope + (keras ? "/gamma" : "/bn/gamma"));
+  const HostTensor* b = find_w(m, scope + (keras ? "/beta" : "/bn/beta"));
+  const HostTensor* mu = find_w(m, scope + (keras ? "/moving_mean" : "/bn/mean/EMA"));
+  const HostTensor* var = find_w(m, scope + (keras ? "/moving_variance" : "/bn/variance/EMA"));
+  ODT_CHECK(g && b && mu && var, "missing BN variables for " + scope);
+  ODT_CHECK(g->data.size() == (size_t)c && b->data.size() == (size_t)c && mu->data.size() == (size_t)c &&
+            var->data.size() == (size_t)c, "bad BN shapes for " + scope);
+  scale->resize(c); shift->resize(c);
+  for (int o = 0; o < c; ++o) {
+    const double inv = (double)g->data[o] / std::sqrt((double)var->data[o] + eps);
+    (*scale)[o] = inv;
+    (*shift)[o] = (double)b->data[o] - (double)mu->data[o] * inv;
+  }
+  return 0;
+}
+
 // Upload conv weights in [Cout][kh][kw][Cin] with optional folded BN; returns device ptrs.
 int upload_conv(odt_model* m, const std::string& scope, int kh, int kw, int cin, int cout,
                 bool has_bn, const float** wt_out, const float** bias_out) {
@@ -44,16 +74,7 @@ int upload_conv(odt_model* m, const std::string& scope, int kh, int kw, int cin,
             "bad shape for " + scope + "/W");
   std::vector<double> scale(cout, 1.0), shift(cout, 0.0);
   if (has_bn) {
-    const HostTensor* g = find_w(m, scope + "/bn/gamma");
-    const HostTensor* b = find_w(m, scope + "/bn/beta");
-    const HostTensor* mu = find_w(m, scope + "/bn/mean/EMA");
-    const HostTensor* var = find_w(m, scope + "/bn/variance/EMA");
-    ODT_CHECK(g && b && mu && var, "missing BN variables for " + scope);
-    for (int o = 0; o < cout; ++o) {   // tf.nn.batch_normalization, eps 1e-5 (nn.py:1771-1774)
-      const double inv = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5);
-      scale[o] = inv;
-      shift[o] = (double)b->data[o] - (double)mu->data[o] * inv;
-    }
+    if (bn_fold(m, scope, cout, 1e-5, false, &scale, &shift)) return 1;
   } else {
     const HostTensor* b = find_w(m, scope + "/b");
     ODT_CHECK(b != nullptr, "missing bias " + scope + "/b");
@@ -67,13 +88,7 @@ int upload_conv(odt_model* m, const std::string& scope, int kh, int kw, int cin,
           wt[(((size_t)o * kh + y) * kw + x) * cin + i] =
               (float)((double)W->data[(((size_t)y * kw + x) * cin + i) * cout + o] * scale[o]);
   for (int o = 0; o < cout; ++o) bias[o] = (float)shift[o];
-  float* dw = m->alloc_f(wt.size(), false);
-  float* db = m->alloc_f(bias.size(), false);
-  ODT_CHECK(dw && db, "device allocation failed for weights of " + scope);
-  ODT_HIP(hipMemcpy(dw, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice));
-  ODT_HIP(hipMemcpy(db, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
-  *wt_out = dw; *bias_out = db;
-  return 0;
+  return upload_raw(m, wt, wt_out) || upload_raw(m, bias, bias_out);
 }
 
 // conv3 + convshortcut of a stage-entry bottleneck as ONE 1x1 conv over the K-concatenated input
@@ -82,7 +97,7 @@ int upload_conv(odt_model* m, const std::string& scope, int kh, int kw, int cin,
 int upload_conv_cat(odt_model* m, const std::string& sa, int cin_a, const std::string& sb, int cin_b, int cout,
                     const float** wt_out, const float** bias_out) {
   std::vector<float> wt((size_t)cout * (cin_a + cin_b));
-  std::vector<double> shift(cout, 0.0);
+  std::vector<double> shift(cout, 0.0), inv, sh;
   const std::string scopes[2] = {sa, sb};
   const int cins[2] = {cin_a, cin_b};
   int koff = 0;
@@ -90,50 +105,31 @@ int upload_conv_cat(odt_model* m, const std::string& sa, int cin_a, const std::s
     const std::string& scope = scopes[part];
     const int cin = cins[part];
     const HostTensor* W = find_w(m, scope + "/W");
-    const HostTensor* g = find_w(m, scope + "/bn/gamma");
-    const HostTensor* b = find_w(m, scope + "/bn/beta");
-    const HostTensor* mu = find_w(m, scope + "/bn/mean/EMA");
-    const HostTensor* var = find_w(m, scope + "/bn/variance/EMA");
-    ODT_CHECK(W && g && b && mu && var, "missing variables for " + scope);
+    ODT_CHECK(W != nullptr, "missing weight " + scope + "/W");
     ODT_CHECK(W->data.size() == (size_t)cin * cout, "bad shape for " + scope + "/W");
+    if (bn_fold(m, scope, cout, 1e-5, false, &inv, &sh)) return 1;
     for (int o = 0; o < cout; ++o) {
-      const double inv = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5);
-      shift[o] += (double)b->data[o] - (double)mu->data[o] * inv;
+      shift[o] += sh[o];
       for (int i = 0; i < cin; ++i)
-        wt[(size_t)o * (cin_a + cin_b) + koff + i] = (float)((double)W->data[(size_t)i * cout + o] * inv);
+        wt[(size_t)o * (cin_a + cin_b) + koff + i] = (float)((double)W->data[(size_t)i * cout + o] * inv[o]);
     }
     koff += cin;
   }
   std::vector<float> bias(cout);
   for (int o = 0; o < cout; ++o) bias[o] = (float)shift[o];
-  float* dw = m->alloc_f(wt.size(), false);
-  float* db = m->alloc_f(bias.size(), false);
-  ODT_CHECK(dw && db, "device allocation failed for weights of " + sa);
-  ODT_HIP(hipMemcpy(dw, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice));
-  ODT_HIP(hipMemcpy(db, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
-  *wt_out = dw; *bias_out = db;
-  return 0;
+  return upload_raw(m, wt, wt_out) || upload_raw(m, bias, bias_out);
 }
 
 // The ResNeXt block's grouped conv2 (W [3,3,C/32,C], nn.py:536-539) with its BN folded in double, as upload_conv does, and
 // re-packed for the kernel (group_conv_pack_weights).
 int upload_group_conv(odt_model* m, const std::string& scope, int C, const float** wt_out, const float** bias_out) {
   const HostTensor* W = find_w(m, scope + "/W");
-  const HostTensor* g = find_w(m, scope + "/bn/gamma");
-  const HostTensor* b = find_w(m, scope + "/bn/beta");
-  const HostTensor* mu = find_w(m, scope + "/bn/mean/EMA");
-  const HostTensor* var = find_w(m, scope + "/bn/variance/EMA");
   ODT_CHECK(W != nullptr, "missing weight " + scope + "/W");
-  ODT_CHECK(g && b && mu && var, "missing BN variables for " + scope);
   ODT_CHECK(W->data.size() == group_conv_weight_elems(C), "bad shape for " + scope + "/W (a 32-group 3x3 conv: [3,3,C/32,C])");
-  ODT_CHECK(g->data.size() == (size_t)C && b->data.size() == (size_t)C && mu->data.size() == (size_t)C &&
-            var->data.size() == (size_t)C, "bad BN shapes for " + scope);
-  std::vector<double> scale(C);
+  std::vector<double> scale, shift;
+  if (bn_fold(m, scope, C, 1e-5, false, &scale, &shift)) return 1;
   std::vector<float> bias(C), img(group_conv_weight_elems(C));
-  for (int o = 0; o < C; ++o) {
-    scale[o] = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5);
-    bias[o] = (float)((double)b->data[o] - (double)mu->data[o] * scale[o]);
-  }
+  for (int o = 0; o < C; ++o) bias[o] = (float)shift[o];
   if (group_conv_pack_weights(W->data.data(), scale.data(), C, img.data())) return 1;
   return upload_raw(m, img, wt_out) || upload_raw(m, bias, bias_out);
 }
@@ -161,28 +157,21 @@ int upload_se_gate(odt_model* m, const std::string& pre, int ch, const float** w
                    const float** b2) {
   const int C4 = ch * 4, r = ch / 4;
   const HostTensor* W3 = find_w(m, pre + "/conv3/W");
-  const HostTensor* g = find_w(m, pre + "/conv3/bn/gamma");
-  const HostTensor* be = find_w(m, pre + "/conv3/bn/beta");
-  const HostTensor* mu = find_w(m, pre + "/conv3/bn/mean/EMA");
-  const HostTensor* var = find_w(m, pre + "/conv3/bn/variance/EMA");
   const HostTensor* f1 = find_w(m, pre + "/fc1/W");
   const HostTensor* f1b = find_w(m, pre + "/fc1/b");
   const HostTensor* f2 = find_w(m, pre + "/fc2/W");
   const HostTensor* f2b = find_w(m, pre + "/fc2/b");
-  ODT_CHECK(W3 && g && be && mu && var, "missing conv3 variables for the SE gate of " + pre);
+  ODT_CHECK(W3 != nullptr, "missing conv3 variables for the SE gate of " + pre);
   ODT_CHECK(f1 && f1b && f2 && f2b, "missing squeeze-excitation variables " + pre + "/fc1, fc2");
-  ODT_CHECK(W3->data.size() == (size_t)ch * C4 && g->data.size() == (size_t)C4 && be->data.size() == (size_t)C4 &&
-            mu->data.size() == (size_t)C4 && var->data.size() == (size_t)C4, "bad conv3 shapes for the SE gate of " + pre);
+  ODT_CHECK(W3->data.size() == (size_t)ch * C4, "bad conv3 shapes for the SE gate of " + pre);
   ODT_CHECK(f1->data.size() == (size_t)C4 * r && f1b->data.size() == (size_t)r && f2->data.size() == (size_t)r * C4 &&
             f2b->data.size() == (size_t)C4, "bad squeeze-excitation shapes in " + pre);
-  std::vector<double> scale(C4), acc(r);
+  std::vector<double> scale, shift, acc(r);
+  if (bn_fold(m, pre + "/conv3", C4, 1e-5, false, &scale, &shift)) return 1;
   std::vector<float> v1((size_t)r * ch), vb(r);
   for (int j = 0; j < r; ++j) acc[j] = (double)f1b->data[j];
-  for (int o = 0; o < C4; ++o) {
-    scale[o] = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5);
-    const double shift = (double)be->data[o] - (double)mu->data[o] * scale[o];
-    for (int j = 0; j < r; ++j) acc[j] += shift * (double)f1->data[(size_t)o * r + j];
-  }
+  for (int o = 0; o < C4; ++o)
+    for (int j = 0; j < r; ++j) acc[j] += shift[o] * (double)f1->data[(size_t)o * r + j];
   for (int j = 0; j < r; ++j) vb[j] = (float)acc[j];
   for (int i = 0; i < ch; ++i) {
     std::fill(acc.begin(), acc.end(), 0.0);
@@ -204,31 +193,33 @@ int upload_raw(odt_model* m, const std::vector<float>& v, const float** out) {
   return 0;
 }
 
-// Append a conv op.  `in` logical dims (h,w) bound the reads; output tensor is created here
-// unless `out_existing` is given.
-int add_conv(odt_model* m, const std::string& name, const Tensor& in, int cin, const float* wt,
-             const float* bias, int kh, int kw, int cout, int stride, int dil, int pad_t, int pad_l,
-             int Ho, int Wo, int oy, int ox, const Tensor* res, int res_mode, bool relu,
-             int out_ldc, Tensor* out, const std::string& tap) {
+// Append the conv op of `s`.  The output tensor is created here unless `out` already holds one.
+int add_conv(odt_model* m, const ConvSpec& s, Tensor* out) {
   ConvOp c;
-  c.name = name;
+  c.name = s.name;
   ConvParams& p = c.p;
   std::memset(&p, 0, sizeof(p));
+  const Tensor& in = s.in;
+  const int Ho = s.Ho >= 0 ? s.Ho : in.h, Wo = s.Wo >= 0 ? s.Wo : in.w;
+  const int out_ldc = s.out_ldc >= 0 ? s.out_ldc : s.cout;
   if (out->d == nullptr) {
-    if (make_tensor(m, tap, in.B, Ho + oy, Wo + ox, out_ldc, out, oy != 0 || ox != 0 || out_ldc != cout))
+    if (make_tensor(m, s.tap, in.B, Ho + s.oy, Wo + s.ox, out_ldc, out, s.oy != 0 || s.ox != 0 || out_ldc != s.cout))
       return 1;
-    out->c = cout;
+    out->c = s.cout;
   }
-  p.in = in.d; p.wt = wt; p.bias = bias; p.out = out->d;
-  p.res = res ? res->d : nullptr;
-  p.B = in.B; p.H = in.h; p.W = in.w; p.Cin = cin; p.in_ldc = in.C;
+  p.in = in.d; p.wt = s.wt; p.bias = s.bias; p.out = out->d;
+  p.res = s.res ? s.res->d : nullptr;
+  p.B = in.B; p.H = in.h; p.W = in.w; p.Cin = s.cin; p.in_ldc = in.C;
   p.in_Ha = in.H; p.in_Wa = in.W;   // sliced views keep the allocation pitch
-  p.Ho = Ho; p.Wo = Wo; p.Cout = cout;
-  p.kh = kh; p.kw = kw; p.stride = stride; p.dil = dil; p.pad_t = pad_t; p.pad_l = pad_l;
-  p.out_H = out->H; p.out_W = out->W; p.out_oy = oy; p.out_ox = ox; p.out_ldc = out->C;
-  p.res_mode = res ? res_mode : 0;
-  if (res) { p.res_H = res->H; p.res_W = res->W; p.res_ldc = res->C; }
-  p.relu = relu ? 1 : 0;
+  p.Ho = Ho; p.Wo = Wo; p.Cout = s.cout;
+  p.kh = s.kh; p.kw = s.kw; p.stride = s.stride; p.dil = s.dil; p.pad_t = s.pad_t; p.pad_l = s.pad_l;
+  p.out_H = out->H; p.out_W = out->W; p.out_oy = s.oy; p.out_ox = s.ox; p.out_ldc = out->C;
+  p.res_mode = s.res ? s.res_mode : 0;
+  if (s.res) { p.res_H = s.res->H; p.res_W = s.res->W; p.res_ldc = s.res->C; }
+  p.relu = s.relu;
+  if (s.in2) {
+    p.in2 = s.in2->d; p.Cin2 = s.cin2; p.in2_ldc = s.in2->C; p.in2_Ha = s.in2->H; p.in2_Wa = s.in2->W; p.in2_stride = s.in2_stride;
+  }
   conv_prepare(p);
   m->convs.push_back(c);
   Op op;
@@ -237,7 +228,6 @@ int add_conv(odt_model* m, const std::string& name, const Tensor& in, int cin, c
   m->ops.push_back(op);
   return 0;
 }
-
 
 // A handle's side streams (tail, H2D, D2H) are created with the highest stream priority.  Not for the arbitration: the
 // runtime multiplexes all streams of ONE priority onto a few hardware queues in creation order, and a side stream that

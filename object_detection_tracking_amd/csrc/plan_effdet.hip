@@ -64,20 +64,6 @@ std::vector<EffBlock> eff_blocks(int variant, int* stem) {
   return v;
 }
 
-// BN fold factors of a Keras BatchNormalization scope (gamma, beta, moving_mean, moving_variance)
-int eff_bn(odt_model* m, const std::string& scope, int c, std::vector<double>* scale, std::vector<double>* shift) {
-  const HostTensor* g = find_w(m, scope + "/gamma"); const HostTensor* b = find_w(m, scope + "/beta");
-  const HostTensor* mu = find_w(m, scope + "/moving_mean"); const HostTensor* var = find_w(m, scope + "/moving_variance");
-  ODT_CHECK(g && b && mu && var, "missing BN variables for " + scope);
-  ODT_CHECK((int)g->data.size() == c && (int)var->data.size() == c, "bad BN shape for " + scope);
-  scale->resize(c); shift->resize(c);
-  for (int o = 0; o < c; ++o) {
-    const double inv = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-3);
-    (*scale)[o] = inv; (*shift)[o] = (double)b->data[o] - (double)mu->data[o] * inv;
-  }
-  return 0;
-}
-
 // 1x1 conv weights [1,1,cin,cout] (+ BN scope or bias) -> device [cout][cin_pad] + bias[cout]
 int eff_upload_pw(odt_model* m, const std::string& conv, const std::string& bn_scope, bool has_bias, int cin,
                   int cin_pad, int cout, const float** wt_out, const float** bias_out,
@@ -85,7 +71,7 @@ int eff_upload_pw(odt_model* m, const std::string& conv, const std::string& bn_s
   const HostTensor* W = find_w(m, conv + "/" + kernel_name);
   ODT_CHECK(W != nullptr && W->data.size() == (size_t)cin * cout, "missing / bad " + conv + "/" + kernel_name);
   std::vector<double> scale(cout, 1.0), shift(cout, 0.0);
-  if (!bn_scope.empty() && eff_bn(m, bn_scope, cout, &scale, &shift)) return 1;
+  if (!bn_scope.empty() && bn_fold(m, bn_scope, cout, 1e-3, true, &scale, &shift)) return 1;
   if (has_bias) {
     const HostTensor* b = find_w(m, conv + "/bias");
     ODT_CHECK(b != nullptr && (int)b->data.size() == cout, "missing / bad " + conv + "/bias");
@@ -108,13 +94,6 @@ struct EffDetCfg { int filters, cells, repeats; bool fastattn; };
 EffDetCfg effdet_cfg(int d) {
   static const int T[8][3] = {{64, 3, 3}, {88, 4, 3}, {112, 5, 3}, {160, 6, 4}, {224, 7, 4}, {288, 7, 4}, {384, 8, 5}, {384, 8, 5}};
   return EffDetCfg{T[d][0], T[d][1], T[d][2], d != 7};
-}
-
-int eff_same(int n, int k, int s, int* before) {
-  const int out = (n + s - 1) / s;
-  const int tot = std::max((out - 1) * s + k - n, 0);
-  *before = tot / 2;
-  return out;
 }
 
 // depthwise 3x3 'same' (no BN, no activation) + pointwise 1x1 (+bias, optional BN fold, activation)
@@ -140,9 +119,9 @@ int eff_sepconv(odt_model* m, const std::string& scope, const std::string& bn_sc
   const float *wt, *bias;
   if (eff_upload_pw(m, scope, bn_scope, true, cin, ldc, cout, &wt, &bias, "pointwise_kernel")) return 1;
   // the pointwise bias variable of separable_conv2d is "<scope>/bias"
-  if (add_conv(m, scope, t1, ldc, wt, bias, 1, 1, cout, 1, 1, 0, 0, in.h, in.w, 0, 0, nullptr, 0, false, r32(m, cout), out, tap)) return 1;
-  m->convs.back().p.relu = act;
-  return 0;
+  ConvSpec c(scope, t1, ldc, cout);
+  c.wt = wt; c.bias = bias; c.relu = act; c.out_ldc = r32(m, cout); c.tap = tap;
+  return add_conv(m, c, out);
 }
 
 int build_effdet_heads(odt_model* m, const Tensor* red, const int* red_ch) {
@@ -166,13 +145,16 @@ int build_effdet_heads(odt_model* m, const Tensor* red, const int* red_ch) {
     if (f.ch == F) { *out = f.t; return 0; }
     if (eff_upload_pw(m, scope + "/conv2d", scope + "/bn", true, f.ch, f.t.C, F, &wt, &bias)) return 1;
     *out = Tensor{};
-    return add_conv(m, scope + "/conv2d", f.t, f.t.C, wt, bias, 1, 1, F, 1, 1, 0, 0, f.t.h, f.t.w, 0, 0, nullptr, 0, false, LF, out, "");
+    ConvSpec c(scope + "/conv2d", f.t, f.t.C, F);
+    c.wt = wt; c.bias = bias; c.out_ldc = LF;
+    return add_conv(m, c, out);
   };
   auto fuse_input = [&](FuseParams& fp, int k, const Tensor& t, int th, int tw) {
     fp.in[k] = t.d; fp.ih[k] = t.h; fp.iw[k] = t.w; fp.sy[k] = fp.sx[k] = 1.f; fp.pt[k] = fp.pl[k] = 0;
     if (t.h > th && t.w > tw) {
-      int pb; ODT_CHECK(eff_same(t.h, 3, 2, &pb) == th, "BiFPN: unsupported down-sampling ratio"); fp.pt[k] = pb;
-      ODT_CHECK(eff_same(t.w, 3, 2, &pb) == tw, "BiFPN: unsupported down-sampling ratio"); fp.pl[k] = pb;
+      int ho, wo;
+      same_pad(t.h, 3, 2, &ho, &fp.pt[k]); same_pad(t.w, 3, 2, &wo, &fp.pl[k]);
+      ODT_CHECK(ho == th && wo == tw, "BiFPN: unsupported down-sampling ratio");
       fp.mode[k] = 2;
     } else if (t.h > th || t.w > tw) {
       ODT_CHECK(false, "BiFPN: incompatible feature map sizes (efficientdet_arch.py:196-199): every pyramid level "
@@ -296,9 +278,9 @@ int build_effdet_heads(odt_model* m, const Tensor* red, const int* red_ch) {
       const float *wt, *bias;
       if (eff_upload_pw(m, scope, "", true, F, LF, cout, &wt, &bias, "pointwise_kernel")) return 1;
       const int lco = r32(m, cout);
-      if (add_conv(m, scope, t1, LF, wt, bias, 1, 1, cout, 1, 1, 0, 0, Mtot / 256, 256, 0, 0, nullptr, 0, false, lco, out, "")) return 1;
-      ConvParams& cp = m->convs.back().p;
-      cp.relu = act;
+      ConvSpec c(scope, t1, LF, cout);
+      c.wt = wt; c.bias = bias; c.relu = act; c.out_ldc = lco;
+      if (add_conv(m, c, out)) return 1;
       if (!bn_prefix.empty()) {
         // per-level BatchNorm in the epilogue: out = (W x) * inv_l + (beta_l - mean_l * inv_l + b * inv_l)
         const HostTensor* pb = find_w(m, scope + "/bias");
@@ -306,7 +288,7 @@ int build_effdet_heads(odt_model* m, const Tensor* red, const int* red_ch) {
         std::vector<float> sc((size_t)5 * lco, 1.f), sh((size_t)5 * lco, 0.f);
         for (int l = 0; l < 5; ++l) {
           std::vector<double> scale, shift;
-          if (eff_bn(m, bn_prefix + std::to_string(l + 3), cout, &scale, &shift)) return 1;
+          if (bn_fold(m, bn_prefix + std::to_string(l + 3), cout, 1e-3, true, &scale, &shift)) return 1;
           for (int o = 0; o < cout; ++o) {
             sc[(size_t)l * lco + o] = (float)scale[o];
             sh[(size_t)l * lco + o] = (float)(shift[o] + (double)pb->data[o] * scale[o]);
@@ -314,6 +296,7 @@ int build_effdet_heads(odt_model* m, const Tensor* red, const int* red_ch) {
         }
         const float *dsc, *dsh;
         if (upload_raw(m, sc, &dsc) || upload_raw(m, sh, &dsh)) return 1;
+        ConvParams& cp = m->convs.back().p;
         cp.bias = dsh; cp.lvl_scale = dsc; cp.nlvl = 5; cp.lvl_stride = lco;
         for (int l = 0; l < 5; ++l) cp.lvl_start[l] = off[l];      // (all five in use; fewer ranges: fill the rest with INT_MAX)
       }
@@ -414,15 +397,9 @@ int build_plan_effnet(odt_model* m) {
   const std::string name = "efficientnet-b" + std::to_string(cfg.eff_backbone);
   int stemC = 0;
   const std::vector<EffBlock> blocks = eff_blocks(cfg.eff_backbone, &stemC);
-  auto same = [](int n, int k, int s, int* out, int* before) {
-    *out = (n + s - 1) / s;
-    const int tot = std::max((*out - 1) * s + k - n, 0);
-    *before = tot / 2;
-    return tot;
-  };
   // ---- input: normalised RGB, HWC4, physically padded with the stem's 'SAME' pads
   int Ho, Wo, pt, pl;
-  const int ph = same(H, 3, 2, &Ho, &pt), pw = same(W, 3, 2, &Wo, &pl);
+  const int ph = same_pad(H, 3, 2, &Ho, &pt), pw = same_pad(W, 3, 2, &Wo, &pl);
   m->Hp = H + ph; m->Wp = std::max(W + pw, 2 * (Wo - 1) + 8);
   if (make_tensor(m, "image_pad", B, m->Hp, m->Wp, 4, &m->image_pad, true)) return 1;
   m->frames_bytes = (size_t)B * H * W * 3 * sizeof(float);
@@ -436,7 +413,7 @@ int build_plan_effnet(odt_model* m) {
     const HostTensor* W0 = find_w(m, name + "/stem/conv2d/kernel");
     ODT_CHECK(W0 && W0->data.size() == (size_t)3 * 3 * 3 * stemC, "missing / bad " + name + "/stem/conv2d/kernel");
     std::vector<double> scale, shift;
-    if (eff_bn(m, name + "/stem/tpu_batch_normalization", stemC, &scale, &shift)) return 1;
+    if (bn_fold(m, name + "/stem/tpu_batch_normalization", stemC, 1e-3, true, &scale, &shift)) return 1;
     std::vector<float> v((size_t)stemC * 3 * 32, 0.f), bv(stemC);
     for (int o = 0; o < stemC; ++o) {
       for (int y = 0; y < 3; ++y) for (int x = 0; x < 3; ++x) for (int c = 0; c < 3; ++c)
@@ -446,9 +423,11 @@ int build_plan_effnet(odt_model* m) {
     if (upload_raw(m, v, &wt) || upload_raw(m, bv, &bias)) return 1;
   }
   Tensor x{};
-  if (add_conv(m, "stem", m->image_pad, 32, wt, bias, 3, 1, stemC, 2, 1, 0, 0, Ho, Wo, 0, 0, nullptr, 0, false,
-               r32(m, stemC), &x, "stem")) return 1;
-  m->convs.back().p.relu = 2;
+  {
+    ConvSpec c("stem", m->image_pad, 32, stemC);
+    c.wt = wt; c.bias = bias; c.kh = 3; c.stride = 2; c.Ho = Ho; c.Wo = Wo; c.relu = 2; c.out_ldc = r32(m, stemC); c.tap = "stem";
+    if (add_conv(m, c, &x)) return 1;
+  }
   // ---- MBConv blocks
   Tensor red_feats[6]; int red_ch[6] = {0, 0, 0, 0, 0, 0};
   for (const EffBlock& b : blocks) {
@@ -460,7 +439,7 @@ int build_plan_effnet(odt_model* m) {
     const Tensor inp = x;
     Tensor t1 = x;
     int ho, wo, dpt, dpl;
-    same(x.h, b.kernel, b.stride, &ho, &dpt); same(x.w, b.kernel, b.stride, &wo, &dpl);
+    same_pad(x.h, b.kernel, b.stride, &ho, &dpt); same_pad(x.w, b.kernel, b.stride, &wo, &dpl);
     const int fmode = eff_fuse_mb_mode(m);
     const bool fuse_mb = b.expand != 1 && eff_split_on(m) && x.C % 32 == 0 && lmid % 64 == 0 && x.h == x.H && x.w == x.W &&
                          (fmode >= 2 || (fmode == 1 && std::min(ho, wo) >= eff_fuse_mb_min(m)));
@@ -470,8 +449,9 @@ int build_plan_effnet(odt_model* m) {
       if (eff_upload_pw(m, cn, bn, false, b.cin, x.C, mid, &ewt, &ebias)) return 1;
       if (!fuse_mb) {
         t1 = Tensor{};
-        if (add_conv(m, cn, x, x.C, ewt, ebias, 1, 1, mid, 1, 1, 0, 0, x.h, x.w, 0, 0, nullptr, 0, false, lmid, &t1, "")) return 1;
-        m->convs.back().p.relu = 2;
+        ConvSpec c(cn, x, x.C, mid);
+        c.wt = ewt; c.bias = ebias; c.relu = 2; c.out_ldc = lmid;
+        if (add_conv(m, c, &t1)) return 1;
       }
     }
     // depthwise + BN + swish
@@ -482,7 +462,7 @@ int build_plan_effnet(odt_model* m) {
       const HostTensor* Wd = find_w(m, p + "depthwise_conv2d/depthwise_kernel");
       ODT_CHECK(Wd && Wd->data.size() == (size_t)b.kernel * b.kernel * mid, "missing / bad " + p + "depthwise_conv2d/depthwise_kernel");
       std::vector<double> scale, shift;
-      if (eff_bn(m, bname(), mid, &scale, &shift)) return 1;
+      if (bn_fold(m, bname(), mid, 1e-3, true, &scale, &shift)) return 1;
       std::vector<float> v((size_t)b.kernel * b.kernel * lmid, 0.f), bv(lmid, 0.f);
       for (int t = 0; t < b.kernel * b.kernel; ++t)
         for (int c = 0; c < mid; ++c) v[(size_t)t * lmid + c] = (float)((double)Wd->data[(size_t)t * mid + c] * scale[c]);
@@ -573,8 +553,9 @@ int build_plan_effnet(odt_model* m) {
         m->ops.push_back(wsop);
         wt_run = ws;
       }
-      if (add_conv(m, cn, t2, lmid, wt_run, bias, 1, 1, b.cout, 1, 1, 0, 0, ho, wo, 0, 0, skip ? &inp : nullptr, 1, false,
-                   r32(m, b.cout), &y, tap)) return 1;
+      ConvSpec c(cn, t2, lmid, b.cout);
+      c.wt = wt_run; c.bias = bias; c.res = skip ? &inp : nullptr; c.res_mode = 1; c.out_ldc = r32(m, b.cout); c.tap = tap;
+      if (add_conv(m, c, &y)) return 1;
       if (b.reduction) { m->taps["reduction_" + std::to_string(b.reduction)] = y; red_feats[b.reduction] = y; red_ch[b.reduction] = b.cout; }
       x = y;
     }
