@@ -115,6 +115,11 @@ typedef struct odt_config {
                              * row offsets, odd ones column offsets, tap-major) and conv2/W [3,3,C,C] without conv2/bn: the nine taps are
                              * bilinear samples at clamped coordinates, each image with its own offsets.  block_kind 0 without use_se
                              * only; not with use_dilations (the reference graph does not build) */
+  int32_t use_gn;           /* --use_gn (nn.py:81-108): GroupNorm (32 groups, eps 1e-5, statistics per image) in place of every BatchNorm of
+                             * the backbone -- variables conv0/gn/{gamma,beta}, groupG/blockI/{conv1,conv2,conv3,convshortcut}/gn/{gamma,beta}
+                             * -- and behind every FPN lateral and posthoc conv (fpn/gn_cN, fpn/gn_pN; nn.py:987-1009).  Nothing is folded
+                             * into the conv weights: each normalised conv is followed by the launches of csrc/group_norm.hip, which carry its
+                             * ReLU / residual / top-down add.  block_kind 0 without use_se and use_deformable only */
 } odt_config;
 
 /* conv_arith: all modes keep f32 tensors and f32 accumulation.  ODT_ARITH_F32: every product on the exact-f32 MFMA
@@ -529,6 +534,16 @@ int odt_op_deform_conv(int device, const float* x, int B, int H, int W, int C, c
  * 0) and the op reads rows < H, columns < W, channels < C of it; nothing outside the view is touched. */
 int odt_op_deform_conv_view(int device, const float* x, int B, int Ha, int Wa, int ldc, int H, int W, int C, const float* w_off,
                             const float* b_off, const float* w, float* out, float* out_amax, float* offsets_out);
+/* GroupNorm (csrc/group_norm.hip; --use_gn, nn.py:81-108: group_norm(x, group = 32)) as the plan runs it.  x is [B,Ha,Wa,ldc] (ldc % 4 ==
+ * 0); the op normalises the view of h rows, w columns and C channels (C % 32 == 0) at row oy, column ox of every image -- per image and
+ * per group of C / 32 adjacent channels: mean and biased variance over the view (f64 sums in a fixed order), a = rsqrt(var + eps) *
+ * gamma[c], y = x * a + (beta[c] - mean * a) in f32 -- then adds the residual (res_mode 0 none | 1 res [B,res_H,res_W,C], the same
+ * pixels | 2 res [B,res_H,res_W,C] nearest-2x upsampled) and applies ReLU if relu.  out has x's geometry and comes back as it went
+ * in outside the view.  chunks: row ranges per image of the statistics pass, 0 = the launcher's choice (a test argument).  amax
+ * [1]: the |max| the kernel recorded for out; mean, var [B,32]. */
+int odt_op_group_norm(int device, const float* x, int B, int Ha, int Wa, int ldc, int h, int w, int C, int oy, int ox,
+                      const float* gamma, const float* beta, float eps, int relu, int res_mode, const float* res, int res_H,
+                      int res_W, int chunks, float* out, float* amax, float* mean, float* var);
 /* BiFPN node input fusion (launch_bifpn_fuse): n = 1..3 inputs ins[k] [B,in_hw[k][0],in_hw[k][1],ldc], mode[k] 0 same
  * size, 1 nearest resize, 2 3x3 / s2 'SAME' max pool with pads[k] = (top, left); wsm != NULL: 'fastattn' with the raw
  * WSM scalars [n], else a plain sum; act 0 / 2 (swish).  out [B,h,w,ldc]. */

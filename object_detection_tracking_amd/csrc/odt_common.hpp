@@ -461,6 +461,35 @@ int deform_pack_weights(const float* hwio, int C, float* dst);
 // both kernels, in stream order (`between`: an event recorded after the offset kernel, for profiling)
 int launch_deform_conv(const DeformConvParams& p, hipStream_t stream, hipEvent_t between = nullptr);
 
+// ------------------------------------------------------- GroupNorm (group_norm.hip; --use_gn, reference nn.py:81-108)
+// Per image and per group of C / 32 adjacent channels over the h x w view of x: mean and biased variance (f64 sums), then
+// out = x * a + s with a = rsqrt(var + eps) * gamma[c], s = beta[c] - mean * a (f32, the reference's operand order), + the
+// residual as res_mode says, optional ReLU.  x, out and res are NHWC f32 with pitches of their own.
+constexpr int kGnGroups = 32;
+struct GroupNormParams {
+  const float* x;       // [B,Ha,Wa,ldc]; the view is rows [xoy, xoy + h), columns [xox, xox + w), channels < C of every image
+  const float* gamma;   // [C]
+  const float* beta;    // [C]
+  const float* res;     // residual (see res_mode) or nullptr
+  float* out;           // [B,oH,oW,out_ldc]; the view's pixels land at (oy, ox); nothing outside them is written.  May be x
+  double* part;         // scratch [B][32][group_norm_parts][2]: per workgroup (sum, sum of squares)
+  float* ab;            // scratch [B][2][C]: a, then s
+  float* mean;          // [B][32]
+  float* var;           // [B][32]
+  unsigned* amax;       // range slot of out (|max| of what is stored) or nullptr
+  int B, h, w, C;       // C % 32 == 0
+  int Ha, Wa, ldc, xoy, xox;            // ldc, out_ldc, res_ldc multiples of 4
+  int oH, oW, out_ldc, oy, ox;
+  int res_mode;         // 0 none | 1 [B,res_H,res_W,res_ldc], same pixels | 2 nearest-2x upsample of [B,res_H,res_W,res_ldc]
+  int res_H, res_W, res_ldc;
+  int relu;
+  float eps;
+  int chunks;           // row ranges per image of the statistics pass; 0: group_norm_chunks (a function of h, w, C alone)
+};
+int group_norm_chunks(int h, int w, int C);
+int group_norm_parts(int h, int w, int C, int chunks);      // partials per (image, group) that a launch with these sizes writes
+int launch_group_norm(const GroupNormParams& p, hipStream_t stream);
+
 // ------------------------------------------------------- EfficientDet tail (effdet_post.hip)
 struct EffPostParams {
   const float* cls[5];     // per level [B, npix, ldc_cls]  (9 * ncls valid channels: anchor-major)

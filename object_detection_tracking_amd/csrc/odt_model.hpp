@@ -60,12 +60,13 @@ struct ConvOp {
 
 enum OpKind { OP_PRE, OP_CONV, OP_POOL, OP_SUB2, OP_PROPOSALS, OP_ROI_HEAD, OP_DETECT, OP_ROI_FINAL,
               OP_ROI_MASK, OP_MASK_SELECT, OP_PRE_RGB, OP_DW, OP_CMEAN, OP_CSCALE, OP_FUSE, OP_EFF_POST, OP_ROI_EFF, OP_SE_GATE,
-              OP_SE_GATE_MEAN, OP_WSCALE, OP_MB_EXPAND_DW, OP_RSE_GATE, OP_RSE_APPLY, OP_GCONV, OP_BLOCK, OP_DCONV };
+              OP_SE_GATE_MEAN, OP_WSCALE, OP_MB_EXPAND_DW, OP_RSE_GATE, OP_RSE_APPLY, OP_GCONV, OP_BLOCK, OP_DCONV, OP_GN };
 struct Op {
   OpKind kind;
   int conv = -1;        // index into convs (OP_BLOCK: the block's conv2, whose record launches conv_block_kernel)
   int gconv = -1;       // OP_GCONV: its index among the plan's grouped convs (profiling events)
   int dconv = -1;       // OP_DCONV: its index among the plan's deformable convs (profiling events)
+  int gnorm = -1;       // OP_GN: its index among the plan's GroupNorm layers (profiling events)
   Tensor in, out;
   DwConvParams dw{};    // OP_DW
   MbExpandDwParams mb{};   // OP_MB_EXPAND_DW
@@ -75,6 +76,7 @@ struct Op {
   ResSeApplyParams rsa{};   // OP_RSE_APPLY: gate * conv3 + shortcut, ReLU
   GroupConvParams gc{};    // OP_GCONV: the ResNeXt block's 32-group 3x3 conv2 (conv_group.hip)
   DeformConvParams dc{};   // OP_DCONV: a deformable stage entry's conv2_offset + deformable conv2 (conv_deform.hip)
+  GroupNormParams gn{};    // OP_GN: GroupNorm of a conv's output + what that conv's epilogue would have carried (group_norm.hip)
   float* aux = nullptr; // OP_CMEAN: means out [B,ldc]; OP_CSCALE / OP_WSCALE: gates in [B,ldc]
   const float* wt0 = nullptr;   // OP_WSCALE: the conv's unscaled weights [Cout][K] (conv = index of the conv whose weights are rebuilt)
   float* aux2 = nullptr;   // OP_CMEAN: partial-sum scratch
@@ -134,6 +136,7 @@ struct odt_model {
   int se_blocks = 0;                 // SE-ResNet (odt_config.use_se): bottlenecks that run pool + gate + apply (resnet_se.hip)
   int gconv_ops = 0;                 // ResNeXt (odt_config.block_kind == 2): launches of the 32-group 3x3 conv per forward (conv_group.hip)
   int dconv_ops = 0;                 // odt_config.use_deformable: stage entries that run conv2_offset + the deformable conv2 (conv_deform.hip)
+  int gn_ops = 0;                    // odt_config.use_gn: GroupNorm layers, three launches each (group_norm.hip)
   int mb_fused = 0;                  // EfficientNet: MBConv blocks whose expand + depthwise run as one kernel (effnet_mbconv.hip)
   // tail overlap: the selection / ROIAlign / box-head / NMS kernels of forward i (a few dozen workgroups each,
   // ~2 ms per 8-frame step) run on a side stream under the backbone of forward i+1.  The next forward's FPN stage
@@ -182,6 +185,8 @@ struct odt_model {
   double prof_gconv_ms = 0;
   std::vector<hipEvent_t> ev_dconv;  // OP_DCONV i: events [3 i, 3 i + 2] (before, between the two kernels, after)
   double prof_doff_ms = 0, prof_dconv_ms = 0;
+  std::vector<hipEvent_t> ev_gn;     // OP_GN i: events [2 i, 2 i + 1]
+  double prof_gn_ms = 0;
   int prof_forwards = 0;
   int prof_launches = 0;
 
@@ -230,6 +235,8 @@ int upload_conv(odt_model* m, const std::string& scope, int kh, int kw, int cin,
                 const float** bias_out);
 int upload_conv_cat(odt_model* m, const std::string& sa, int cin_a, const std::string& sb, int cin_b, int cout,
                     const float** wt_out, const float** bias_out);
+int upload_conv_plain(odt_model* m, const std::string& scope, int kh, int kw, int cin, int cout, bool has_bias, const float** wt_out,
+                      const float** bias_out);
 int upload_raw(odt_model* m, const std::vector<float>& v, const float** out);
 int upload_group_conv(odt_model* m, const std::string& scope, int C, const float** wt_out, const float** bias_out);
 int upload_deform_conv(odt_model* m, const std::string& pre, int C, const float** wt_off, const float** b_off, const float** wt);
@@ -262,6 +269,7 @@ int fuse_rpn_heads(odt_model* m);
 int fuse_bottleneck_tails(odt_model* m);
 int fuse_bottleneck_blocks(odt_model* m);
 int fuse_stem(odt_model* m);
+int attach_group_norm_scratch(odt_model* m);
 void find_overlap_points(odt_model* m);
 int plan_arena(odt_model* m);
 int upload_conv_records(odt_model* m);
@@ -307,6 +315,8 @@ void visit_op_ptrs(odt_model* m, size_t oi, F&& f) {
     case OP_RSE_APPLY: f(op.rsa.y); f(op.rsa.sc); f(op.rsa.gate); f(op.rsa.out); break;
     case OP_GCONV: f(op.gc.in); f(op.gc.out); break;
     case OP_DCONV: f(op.dc.in); f(op.dc.off); f(op.dc.out); break;
+    // (part / ab / mean / var are dedicated allocations shared by the plan's GroupNorm layers: attach_group_norm_scratch)
+    case OP_GN: f(op.gn.x); f(op.gn.res); f(op.gn.out); break;
     case OP_FUSE: for (auto& p : op.fuse.in) f(p); f(op.fuse.out); break;
     case OP_EFF_POST: for (auto& p : m->eff_post.cls) f(p); for (auto& p : m->eff_post.box) f(p); break;
     case OP_CMEAN: case OP_CSCALE: case OP_SE_GATE: case OP_SE_GATE_MEAN: case OP_WSCALE: case OP_POOL: case OP_SUB2: break;

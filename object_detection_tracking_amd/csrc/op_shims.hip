@@ -1088,6 +1088,38 @@ int odt_op_deform_conv_view(int device, const float* x, int B, int Ha, int Wa, i
   return get_dev(out, dout, npx * C);
 }
 
+int odt_op_group_norm(int device, const float* x, int B, int Ha, int Wa, int ldc, int h, int w, int C, int oy, int ox,
+                      const float* gamma, const float* beta, float eps, int relu, int res_mode, const float* res, int res_H,
+                      int res_W, int chunks, float* out, float* amax, float* mean, float* var) {
+  ODT_CHECK(x && gamma && beta && out && amax && mean && var && (res_mode == 0 || res), "odt_op_group_norm: null argument");
+  ODT_CHECK(B >= 1 && Ha >= 1 && Wa >= 1 && ldc >= 1 && h >= 1 && w >= 1 && C >= 1 && (res_mode == 0 || (res_H >= 1 && res_W >= 1)),
+            "odt_op_group_norm: bad sizes");
+  ODT_CHECK(C % kGnGroups == 0, "odt_op_group_norm: C must be a multiple of 32 (32 groups)");
+  if (set_dev(device)) return 1;
+  GBufs g;
+  GroupNormParams p; std::memset(&p, 0, sizeof(p));
+  const size_t n = (size_t)B * Ha * Wa * ldc;
+  float *dx, *dg, *db, *dres = nullptr, *dout;
+  unsigned* slot;
+  // (out starts as a copy of the caller's buffer: what lies outside the view must come back as it went in)
+  if (g.alloc("x", n, &dx, -1, x) || g.alloc("gamma", (size_t)C, &dg, -1, gamma) || g.alloc("beta", (size_t)C, &db, -1, beta) ||
+      g.alloc("out", n, &dout, -1, out) || g.alloc("range slot", (size_t)kAmaxWays, &slot, 0) ||
+      g.alloc("ab", (size_t)B * 2 * C, &p.ab) || g.alloc("mean", (size_t)B * kGnGroups, &p.mean) || g.alloc("var", (size_t)B * kGnGroups, &p.var)) return 1;
+  if (res_mode != 0 && g.alloc("res", (size_t)B * res_H * res_W * C, &dres, -1, res)) return 1;
+  // (the launcher checks chunks against h; an allocation sized from a bad value must not come first)
+  const int parts = group_norm_parts(h, w, C, chunks >= 1 && chunks <= h ? chunks : 0);
+  if (g.alloc("part", (size_t)B * kGnGroups * parts * 2, &p.part)) return 1;
+  p.x = dx; p.gamma = dg; p.beta = db; p.res = dres; p.out = dout; p.amax = slot;
+  p.B = B; p.h = h; p.w = w; p.C = C; p.Ha = Ha; p.Wa = Wa; p.ldc = ldc; p.xoy = oy; p.xox = ox;
+  p.oH = Ha; p.oW = Wa; p.out_ldc = ldc; p.oy = oy; p.ox = ox;
+  p.res_mode = res_mode; p.res_H = res_H; p.res_W = res_W; p.res_ldc = C; p.relu = relu ? 1 : 0; p.eps = eps; p.chunks = chunks;
+  if (launch_group_norm(p, nullptr)) return 1;
+  if (g.check("odt_op_group_norm")) return 1;
+  if (rse_read_amax(slot, amax)) return 1;
+  if (get_dev(mean, p.mean, (size_t)B * kGnGroups) || get_dev(var, p.var, (size_t)B * kGnGroups)) return 1;
+  return get_dev(out, dout, n);
+}
+
 int odt_op_effdet_post(int device, int B, int ncls, const int32_t* npix, int ldc_cls, int ldc_box,
                        const float* const* cls, const float* const* box, const float* anchors, int k, int max_out,
                        float score_thresh, float iou_thresh, float image_scale, int32_t* cand_idx, float* cand_boxes,

@@ -65,6 +65,9 @@ int bn_fold(odt_model* m, const std::string& scope, int c, double eps, bool kera
   return 0;
 }
 
+static int upload_conv_scaled(odt_model* m, const HostTensor& Wt, int kh, int kw, int cin, int cout, const std::vector<double>& scale,
+                              const std::vector<double>& shift, const float** wt_out, const float** bias_out);
+
 // Upload conv weights in [Cout][kh][kw][Cin] with optional folded BN; returns device ptrs.
 int upload_conv(odt_model* m, const std::string& scope, int kh, int kw, int cin, int cout,
                 bool has_bn, const float** wt_out, const float** bias_out) {
@@ -80,6 +83,30 @@ int upload_conv(odt_model* m, const std::string& scope, int kh, int kw, int cin,
     ODT_CHECK(b != nullptr, "missing bias " + scope + "/b");
     for (int o = 0; o < cout; ++o) shift[o] = b->data[o];
   }
+  return upload_conv_scaled(m, *W, kh, kw, cin, cout, scale, shift, wt_out, bias_out);
+}
+
+// A conv that GroupNorm follows (odt_config.use_gn): the weights as they are -- nothing can be folded, the statistics come from
+// the frame -- with the layer's own bias (the FPN convs) or a zero one (the backbone convs have none).
+int upload_conv_plain(odt_model* m, const std::string& scope, int kh, int kw, int cin, int cout, bool has_bias, const float** wt_out,
+                      const float** bias_out) {
+  const HostTensor* W = find_w(m, scope + "/W");
+  ODT_CHECK(W != nullptr, "missing weight " + scope + "/W");
+  ODT_CHECK(W->data.size() == (size_t)kh * kw * cin * cout, "bad shape for " + scope + "/W");
+  std::vector<double> scale(cout, 1.0), shift(cout, 0.0);
+  if (has_bias) {
+    const HostTensor* b = find_w(m, scope + "/b");
+    ODT_CHECK(b != nullptr, "missing bias " + scope + "/b");
+    ODT_CHECK(b->data.size() == (size_t)cout, "bad shape for " + scope + "/b");
+    for (int o = 0; o < cout; ++o) shift[o] = b->data[o];
+  }
+  return upload_conv_scaled(m, *W, kh, kw, cin, cout, scale, shift, wt_out, bias_out);
+}
+
+// HWIO weights times scale[o] -> [Cout][kh][kw][Cin] and shift -> bias, on the device
+static int upload_conv_scaled(odt_model* m, const HostTensor& Wt, int kh, int kw, int cin, int cout, const std::vector<double>& scale,
+                       const std::vector<double>& shift, const float** wt_out, const float** bias_out) {
+  const HostTensor* W = &Wt;
   std::vector<float> wt((size_t)cout * kh * kw * cin), bias(cout);
   for (int y = 0; y < kh; ++y)
     for (int x = 0; x < kw; ++x)
@@ -346,6 +373,21 @@ int attach_split_weights(odt_model* m) {
       m->range_slot_name[slot] = "deformable conv2 output";
       continue;
     }
+    if (op.kind == OP_GN) {
+      // a GroupNorm layer's output -- the tensor the next convs read: the apply kernel records its range as a conv epilogue
+      // would, so that they keep the fp16x2 kernels (the raw conv output in front has its own slot, which nothing reads)
+      slot_of.erase(op.gn.out);
+      if (pol.family != 2) continue;
+      const int g = tail ? 1 : 0;
+      ODT_CHECK(m->amax_used[g] < odt_model::kAmaxSlots, "too many conv outputs for the range slots");
+      const int slot = (tail ? odt_model::kAmaxSlots : 0) + m->amax_used[g]++;
+      slot_of[op.gn.out] = slot;
+      m->ops[oi].gn.amax = m->amax_dev + (size_t)slot * kAmaxWays;
+      for (const auto& kv : m->taps)
+        if (kv.second.d == op.gn.out) m->range_slot_name[slot] = kv.first + " (GroupNorm)";
+      if (m->range_slot_name[slot].empty()) m->range_slot_name[slot] = "GroupNorm output";
+      continue;
+    }
     if (op.kind == OP_POOL || op.kind == OP_SUB2) {
       auto it = slot_of.find(op.in.d);
       if (it != slot_of.end()) slot_of[op.out.d] = it->second; else slot_of.erase(op.out.d);
@@ -501,6 +543,8 @@ int fuse_bottleneck_tails(odt_model* m) {
   if (m->cfg.use_se) return 0;
   // basic and ResNeXt blocks have no dense 3x3 + 1x1 pair
   if (m->cfg.block_kind != 0) return 0;
+  // GroupNorm stands between conv2 and conv3: conv2's whole output must exist before its statistics do
+  if (m->cfg.use_gn) return 0;
   std::map<const float*, const void*> made;
   for (size_t oi = 0; oi + 1 < m->ops.size(); ++oi) {
     Op& oa = m->ops[oi]; Op& ob = m->ops[oi + 1];
@@ -540,6 +584,7 @@ static int conv_batch_chunks(const ConvParams& p, double limit);
 int fuse_bottleneck_blocks(odt_model* m) {
   if (m->knobs.off(K_FUSE_BLOCK)) return 0;
   if (m->policy.arith == 0 || m->policy.family != 2 || m->cfg.use_se || m->cfg.block_kind != 0) return 0;
+  if (m->cfg.use_gn) return 0;      // (three normalisations inside the block)
   if (m->conv_fused.size() < m->convs.size()) m->conv_fused.resize(m->convs.size(), 0);
   double limit = 2147483648.0;
   if (m->knobs.get(K_CONV_CHUNK_BYTES).d > 0) limit = m->knobs.get(K_CONV_CHUNK_BYTES).d;
@@ -581,6 +626,7 @@ int fuse_bottleneck_blocks(odt_model* m) {
 int fuse_stem(odt_model* m) {
   if (m->knobs.off(K_FUSE_STEM)) return 0;
   if (m->policy.arith == 0 || m->policy.family != 2) return 0;
+  if (m->cfg.use_gn) return 0;      // (conv0's GroupNorm stands between conv0 and pool0)
   for (size_t oi = 0; oi + 1 < m->ops.size(); ++oi) {
     Op& oa = m->ops[oi]; Op& ob = m->ops[oi + 1];
     if (oa.kind != OP_CONV || ob.kind != OP_POOL || oa.skip || ob.skip) continue;
@@ -597,6 +643,31 @@ int fuse_stem(odt_model* m) {
     if (m->knobs.get(K_STEM_GRID).set) ap.debug |= ((int)m->knobs.get(K_STEM_GRID).i & 0x3ff) << 20;   // test knob: workgroups of the launch
     ob.skip = true;
     m->stem_fused = 1;
+  }
+  return 0;
+}
+
+// ---- GroupNorm scratch ------------------------------------------------------------------------------------------------
+// The plan's GroupNorm layers run one after another on the compute stream, all of them in the trunk: they share one buffer of
+// partial sums, one of per-channel factors and one of statistics, each sized for the largest layer.  A layer whose statistics
+// are tapped keeps the buffers it already has.  Called once all ops exist, before plan_arena.
+int attach_group_norm_scratch(odt_model* m) {
+  size_t need_part = 0, need_ab = 0;
+  for (const Op& op : m->ops) {
+    if (op.kind != OP_GN) continue;
+    const GroupNormParams& p = op.gn;
+    need_part = std::max(need_part, (size_t)p.B * kGnGroups * group_norm_parts(p.h, p.w, p.C, p.chunks) * 2);
+    need_ab = std::max(need_ab, (size_t)p.B * 2 * p.C);
+  }
+  if (need_part == 0) return 0;
+  double* part = reinterpret_cast<double*>(m->alloc_f(need_part * 2, false));
+  float* ab = m->alloc_f(need_ab, false);
+  float* stats = m->alloc_f((size_t)m->cfg.batch * kGnGroups * 2, false);
+  ODT_CHECK(part && ab && stats, "device allocation failed (GroupNorm scratch)");
+  for (Op& op : m->ops) {
+    if (op.kind != OP_GN) continue;
+    op.gn.part = part; op.gn.ab = ab;
+    if (op.gn.mean == nullptr) { op.gn.mean = stats; op.gn.var = stats + (size_t)m->cfg.batch * kGnGroups; }
   }
   return 0;
 }

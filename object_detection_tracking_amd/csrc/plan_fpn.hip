@@ -11,10 +11,69 @@ namespace {
 
 constexpr int kFpnStrides[5] = {4, 8, 16, 32, 64};
 
-// upload the weights of the scope `c` is named after (W + folded BN where has_bn, W + b otherwise) and append the conv
+// ---- GroupNorm (--use_gn; nn.py:81-108).  The scope of the gamma / beta that follow conv `name` under odt_config.use_gn: X/gn
+// where the BN graph has X/bn (the backbone), fpn/gn_cN and fpn/gn_pN behind the FPN convs (nn.py:987-1009); "" for every other
+// layer (RPN, heads) and without the flag
+std::string gn_scope(const odt_model* m, const std::string& name, bool has_bn) {
+  if (!m->cfg.use_gn) return "";
+  if (has_bn) return name + "/gn";
+  for (const char* pre : {"fpn/lateral_1x1_", "fpn/posthoc_3x3_"})
+    if (name.compare(0, 16, pre) == 0) return "fpn/gn_" + name.substr(16);
+  return "";
+}
+
+// Append GroupNorm of y over scope/{gamma,beta} with what a conv epilogue would carry: the residual (as ConvParams::res_mode),
+// the ReLU, the output's offset (oy, ox) inside a zero-bordered tensor and its stage name.  Out of place: the normalised
+// tensor is the one the next convs read and gets a range slot of its own (attach_split_weights).  keep_taps handles expose
+// the statistics of conv0's and fpn/gn_p2's layer as "conv0/gn_mean", "conv0/gn_var", "fpn/gn_p2/gn_mean", "fpn/gn_p2/gn_var"
+int add_group_norm(odt_model* m, const std::string& scope, const Tensor& y, int relu, const Tensor* res, int res_mode, int oy, int ox,
+                   const std::string& tap, Tensor* out) {
+  const int C = y.c;
+  ODT_CHECK(relu == 0 || relu == 1, "GroupNorm: " + scope + " is followed by an activation other than ReLU");
+  ODT_CHECK(C % kGnGroups == 0, "GroupNorm: " + scope + " has " + std::to_string(C) + " channels, not a multiple of 32");
+  const HostTensor* g = find_w(m, scope + "/gamma");
+  const HostTensor* b = find_w(m, scope + "/beta");
+  ODT_CHECK(g && b, "missing GroupNorm variables " + scope + "/{gamma,beta} (odt_config.use_gn)");
+  ODT_CHECK(g->data.size() == (size_t)C && b->data.size() == (size_t)C, "bad GroupNorm shapes for " + scope);
+  if (make_tensor(m, tap, y.B, y.h + oy, y.w + ox, C, out, oy != 0 || ox != 0)) return 1;
+  Op op; op.kind = OP_GN; op.out = *out;
+  GroupNormParams& p = op.gn;
+  std::memset(&p, 0, sizeof(p));
+  if (upload_raw(m, g->data, &p.gamma) || upload_raw(m, b->data, &p.beta)) return 1;
+  p.x = y.d; p.out = out->d;
+  p.B = y.B; p.h = y.h; p.w = y.w; p.C = C; p.Ha = y.H; p.Wa = y.W; p.ldc = y.C;
+  p.oH = out->H; p.oW = out->W; p.out_ldc = out->C; p.oy = oy; p.ox = ox;
+  if (res != nullptr && res_mode != 0) { p.res = res->d; p.res_mode = res_mode; p.res_H = res->H; p.res_W = res->W; p.res_ldc = res->C; }
+  p.relu = relu; p.eps = 1e-5f;
+  for (const char* s : {"conv0/gn", "fpn/gn_p2"}) {
+    if (!m->cfg.keep_taps || scope != s) continue;
+    p.mean = m->alloc_f((size_t)y.B * kGnGroups, true); p.var = m->alloc_f((size_t)y.B * kGnGroups, true);
+    ODT_CHECK(p.mean && p.var, "device allocation failed (GroupNorm statistics of " + scope + ")");
+    const std::string name = scope == "conv0/gn" ? "conv0" : scope;
+    Tensor t{}; t.B = 1; t.H = t.h = 1; t.W = t.w = y.B; t.C = t.c = kGnGroups;
+    t.d = p.mean; m->taps[name + "/gn_mean"] = t;
+    t.d = p.var; m->taps[name + "/gn_var"] = t;
+  }
+  op.gnorm = m->gn_ops++;
+  m->ops.push_back(op);
+  return 0;
+}
+
+// upload the weights of the scope `c` is named after (W + folded BN where has_bn, W + b otherwise) and append the conv.  Under
+// odt_config.use_gn a normalised layer is the conv as it is -- nothing folded, no activation, residual or offset -- followed by
+// its GroupNorm, which carries them
 int conv_layer(odt_model* m, ConvSpec c, bool has_bn, Tensor* out) {
-  if (upload_conv(m, c.name, c.kh, c.kw, c.cin, c.cout, has_bn, &c.wt, &c.bias)) return 1;
-  return add_conv(m, c, out);
+  const std::string gn = gn_scope(m, c.name, has_bn);
+  if (gn.empty()) {
+    if (upload_conv(m, c.name, c.kh, c.kw, c.cin, c.cout, has_bn, &c.wt, &c.bias)) return 1;
+    return add_conv(m, c, out);
+  }
+  ConvSpec raw = c;
+  raw.relu = 0; raw.res = nullptr; raw.res_mode = 0; raw.oy = raw.ox = 0; raw.tap = "";
+  if (upload_conv_plain(m, c.name, c.kh, c.kw, c.cin, c.cout, !has_bn, &raw.wt, &raw.bias)) return 1;
+  Tensor y{};
+  if (add_conv(m, raw, &y)) return 1;
+  return add_group_norm(m, gn, y, c.relu, c.res, c.res_mode, c.oy, c.ox, c.tap, out);
 }
 
 // Two 1x1 layers over one input as one: the [cin, na] weights of scope `a` and the [cin, nb] weights of scope `b` side by side
@@ -66,15 +125,23 @@ int front_end(odt_model* m, Tensor* pool) {
           for (int o = 0; o < 64; ++o)
             v.data[((size_t)y * 32 + x * 4 + c) * 64 + o] = W0->data[(((size_t)y * 7 + x) * 3 + c) * 64 + o];
     m->host_w["__conv0v/W"] = v;
-    for (const char* s : {"gamma", "beta", "mean/EMA", "variance/EMA"}) {
-      const HostTensor* t = find_w(m, std::string("conv0/bn/") + s);
-      ODT_CHECK(t != nullptr, std::string("missing conv0/bn/") + s);
-      m->host_w[std::string("__conv0v/bn/") + s] = *t;
+    if (m->cfg.use_gn) {      // conv0 -> GN -> ReLU (nn.py:859-862): the conv alone, conv0/gn behind it
+      if (upload_conv_plain(m, "__conv0v", 7, 1, 32, 64, false, &c0.wt, &c0.bias)) return 1;
+    } else {
+      for (const char* s : {"gamma", "beta", "mean/EMA", "variance/EMA"}) {
+        const HostTensor* t = find_w(m, std::string("conv0/bn/") + s);
+        ODT_CHECK(t != nullptr, std::string("missing conv0/bn/") + s);
+        m->host_w[std::string("__conv0v/bn/") + s] = *t;
+      }
+      if (upload_conv(m, "__conv0v", 7, 1, 32, 64, true, &c0.wt, &c0.bias)) return 1;
     }
-    if (upload_conv(m, "__conv0v", 7, 1, 32, 64, true, &c0.wt, &c0.bias)) return 1;
   }
   Tensor x{};
-  if (add_conv(m, c0, &x)) return 1;
+  if (m->cfg.use_gn) {
+    Tensor y{};
+    c0.relu = 0; c0.tap = "";
+    if (add_conv(m, c0, &y) || add_group_norm(m, "conv0/gn", y, 1, nullptr, 0, 0, 0, "conv0", &x)) return 1;
+  } else if (add_conv(m, c0, &x)) return 1;
   // ---- pool0: pad top/left 1, 3x3 s2 VALID max
   const int Hq = (Ho0 + 1 - 3) / 2 + 1, Wq = (Wo0 + 1 - 3) / 2 + 1;
   if (make_tensor(m, "pool0", B, Hq, Wq, 64, pool)) return 1;
@@ -102,7 +169,9 @@ int shortcut_conv(odt_model* m, const std::string& pre, const Tensor& x, int cou
 // The tail of a bottleneck or ResNeXt block (nn.py:503-521): conv3 (1x1 on t2, to cout channels, BN) + shortcut(x), ReLU
 int conv3_tail(odt_model* m, const Block& b, const Tensor& x, const Tensor& t2, int cout, Tensor* y) {
   const int cin = x.c, Ho = t2.h, Wo = t2.w;
-  if (cin != cout && !m->knobs.off(K_FUSE_SHORTCUT)) {
+  // (under GroupNorm conv3 and the shortcut conv are normalised apart, each with its own statistics: two convs, the
+  // normalised shortcut added as conv3's plain residual)
+  if (cin != cout && !m->knobs.off(K_FUSE_SHORTCUT) && !m->cfg.use_gn) {
     // stage entry: conv3(t2) + convshortcut(x[::stride]) as one K-concatenated GEMM -- saves the
     // shortcut tensor's write + read and one launch (shortcut[:, :, :-1, :-1] of nn.py:555-556
     // never matters: the stride-2 samples stop at 2 * (Ho - 1) <= h - 2)
@@ -247,6 +316,8 @@ int backbone(odt_model* m, Tensor x, Tensor cfeat[4]) {
   ODT_CHECK(cfg.block_kind == 0 || !cfg.use_se, "squeeze-excitation is built for the plain bottleneck only (block_kind 0)");
   ODT_CHECK(!cfg.use_deformable || (cfg.block_kind == 0 && !cfg.use_se),
             "use_deformable is built for the plain bottleneck only (block_kind 0, no squeeze-excitation)");
+  ODT_CHECK(!cfg.use_gn || (cfg.block_kind == 0 && !cfg.use_se && !cfg.use_deformable),
+            "use_gn is built for the plain bottleneck only (block_kind 0, no squeeze-excitation, no deformable conv)");
   for (int g = 0; g < 4; ++g) {
     const int cnt = cfg.num_blocks[g];
     for (int i = 0; i < cnt; ++i) {
@@ -514,6 +585,7 @@ int build_plan(odt_model* m) {
   if (fuse_bottleneck_tails(m)) return 1;
   if (fuse_bottleneck_blocks(m)) return 1;
   if (fuse_stem(m)) return 1;
+  if (attach_group_norm_scratch(m)) return 1;
   if (plan_arena(m)) return 1;
   if (upload_conv_records(m)) return 1;
   return 0;

@@ -143,6 +143,11 @@ static int run_ops(odt_model* m, const void* src, int dtype, hipStream_t st, siz
         if (launch_deform_conv(op.dc, st, m->profile ? m->ev_dconv[3 * op.dconv + 1] : nullptr)) return 1;
         if (m->profile) ODT_HIP(hipEventRecord(m->ev_dconv[3 * op.dconv + 2], st));
         break;
+      case OP_GN:                 // --use_gn: statistics, finalize, apply behind a normalised conv
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_gn[2 * op.gnorm], st));
+        if (launch_group_norm(op.gn, st)) return 1;
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_gn[2 * op.gnorm + 1], st));
+        break;
       case OP_MASK_SELECT:
         if (launch_mask_select(m->mask_sel, st)) return 1;
         break;
@@ -219,6 +224,11 @@ static int finish_profile(odt_model* m, hipStream_t st) {
     ODT_HIP(hipEventElapsedTime(&t1, m->ev_dconv[3 * i + 1], m->ev_dconv[3 * i + 2]));
     m->prof_doff_ms += t0; m->prof_dconv_ms += t1;
   }
+  for (int i = 0; i < m->gn_ops; ++i) {
+    float t = 0;
+    ODT_HIP(hipEventElapsedTime(&t, m->ev_gn[2 * i], m->ev_gn[2 * i + 1]));
+    m->prof_gn_ms += t;
+  }
   ++m->prof_forwards;
   float tt = 0;
   ODT_HIP(hipEventElapsedTime(&tt, m->ev_total[0], m->ev_total[1]));
@@ -266,6 +276,7 @@ int run_plan(odt_model* m, const void* frames, int dtype, int on_device, hipStre
     while (m->ev.size() < 2 * m->convs.size()) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev.push_back(e); }
     while (m->ev_gconv.size() < 2 * (size_t)m->gconv_ops) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_gconv.push_back(e); }
     while (m->ev_dconv.size() < 3 * (size_t)m->dconv_ops) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_dconv.push_back(e); }
+    while (m->ev_gn.size() < 2 * (size_t)m->gn_ops) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_gn.push_back(e); }
     for (int i = 0; i < 2; ++i) if (!m->ev_total[i]) ODT_HIP(hipEventCreate(&m->ev_total[i]));
     ODT_HIP(hipEventRecord(m->ev_total[0], st));
   }
@@ -354,6 +365,7 @@ int odt_destroy(odt_handle h) {
   for (auto e : h->ev) (void)hipEventDestroy(e);
   for (auto e : h->ev_gconv) (void)hipEventDestroy(e);
   for (auto e : h->ev_dconv) (void)hipEventDestroy(e);
+  for (auto e : h->ev_gn) (void)hipEventDestroy(e);
   for (auto e : h->ev_total) if (e) (void)hipEventDestroy(e);
   for (auto& sl : h->slot) {
     if (sl.pin_in) (void)hipHostFree(sl.pin_in);
@@ -707,6 +719,7 @@ int odt_profile_enable(odt_handle h, int enable) {
   h->prof_conv_ms = h->prof_conv_flops = h->prof_total_ms = 0; h->prof_launches = 0;
   h->prof_gconv_ms = 0; h->prof_forwards = 0;
   h->prof_doff_ms = h->prof_dconv_ms = 0;
+  h->prof_gn_ms = 0;
   h->prof_layer_ms.assign(h->convs.size(), 0.0);
   return 0;
 }
@@ -764,6 +777,15 @@ int odt_describe(odt_handle h, char* buf, int cap) {
     for (char& ch : e) if (ch == '"' || ch == '\\' || (unsigned char)ch < 0x20) ch = '?';
     envs += (i ? ", \"" : "\"") + e + "\"";
   }
+  // GroupNorm's byte floor from the plan's own tensors: every layer reads its conv output twice (statistics, apply) and writes
+  // the normalised tensor once; the block tails and the FPN top-down sums read a residual on top
+  double gn_bytes = 0.0;
+  for (const Op& op : h->ops) {
+    if (op.kind != OP_GN) continue;
+    const GroupNormParams& g = op.gn;
+    const double t = 4.0 * g.B * g.h * g.w * g.C;
+    gn_bytes += 3.0 * t + (g.res_mode == 1 ? t : (g.res_mode == 2 ? 4.0 * g.B * ((g.h + 1) / 2) * ((g.w + 1) / 2) * g.C : 0.0));
+  }
   char tmp[8192];
   std::snprintf(tmp, sizeof(tmp),
                 "{\"conv_arith\": \"%s\", \"conv_launches\": %d, \"convs_fused_into_epilogues\": %d, \"exact_f32_mfma_launches\": %d, "
@@ -774,7 +796,8 @@ int odt_describe(odt_handle h, char* buf, int cap) {
                 "\"arena_tensor_bytes_unshared\": %zu, \"dedicated_tensor_bytes\": %zu, \"keep_taps\": %d}, \"convs_cut_into_batch_ranges\": %d, "
                 "\"use_se\": %d, \"se_blocks\": %d, \"se_blocks_conv1_on_fp16x2\": %d, \"block_kind\": \"%s\", \"group_conv_launches\": %d, "
                 "\"group_conv_profiled_ms\": %.6f, \"profiled_forwards\": %d, \"use_deformable\": %d, \"deform_conv_launches\": %d, "
-                "\"deform_offset_profiled_ms\": %.6f, \"deform_conv_profiled_ms\": %.6f}",
+                "\"deform_offset_profiled_ms\": %.6f, \"deform_conv_profiled_ms\": %.6f, \"use_gn\": %d, \"group_norms\": %d, "
+                "\"group_norm_profiled_ms\": %.6f, \"group_norm_floor_bytes\": %.0f}",
                 h->policy.arith != 0 && fam[2] > 0 ? "f32 through fp16x2 / bf16x3 split products"
                     : (h->policy.arith != 0 && fam[1] + fam[3] > 0 ? "f32 through bf16x3 split products" : "exact f32 MFMA"),
                 (int)h->convs.size() - nfused, nfused, fam[0], fam[1] + fam[3], fam[2], h->convs_h2f, h->blocks_fused, h->stem_fused, h->mb_fused, fam[3], fam[1], fam[2], nsk, h->policy.family,
@@ -782,7 +805,8 @@ int odt_describe(odt_handle h, char* buf, int cap) {
                 dev_bytes, h->arena_bytes[0], h->arena_bytes[1], h->vt.size(), h->virtual_tensor_bytes,
                 h->dedicated_tensor_bytes, h->cfg.keep_taps, h->chunked_convs, h->cfg.use_se != 0 ? 1 : 0, h->se_blocks, se_conv1_h2,
                 h->cfg.block_kind == 1 ? "basic" : (h->cfg.block_kind == 2 ? "resnext32x4d" : "bottleneck"), h->gconv_ops,
-                h->prof_gconv_ms, h->prof_forwards, h->cfg.use_deformable != 0 ? 1 : 0, h->dconv_ops, h->prof_doff_ms, h->prof_dconv_ms);
+                h->prof_gconv_ms, h->prof_forwards, h->cfg.use_deformable != 0 ? 1 : 0, h->dconv_ops, h->prof_doff_ms, h->prof_dconv_ms,
+                h->cfg.use_gn != 0 ? 1 : 0, h->gn_ops, h->prof_gn_ms, gn_bytes);
   ODT_CHECK((int)std::strlen(tmp) < cap, "odt_describe: buffer too small");
   std::strncpy(buf, tmp, cap - 1); buf[cap - 1] = 0;
   return 0;

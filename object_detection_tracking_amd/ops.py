@@ -560,6 +560,37 @@ def deform_conv(x, w_off, b_off, w, lib=None, device=0, view=None):
   return out, float(amax[0]), off
 
 
+def group_norm(x, gamma, beta, eps=1e-5, relu=False, res=None, upsample=False, view=None, offset=(0, 0), chunks=0, out_init=None,
+               lib=None, device=0):
+  """GroupNorm as a --use_gn plan runs it (csrc/group_norm.hip; reference nn.py:81-108): x [B,H,W,C], C % 32 == 0, 32 groups of
+  adjacent channels; per image and group mean and biased variance over all positions, a = rsqrt(var + eps) * gamma[c],
+  out = x * a + (beta[c] - mean * a), + res ([B,H,W,C], or [B,ceil(H/2),ceil(W/2),C] nearest-2x upsampled with upsample=True),
+  ReLU if relu.  With view = (h, w, C), x is an allocation [B,Ha,Wa,ldc] of which the op normalises h rows, w columns and C
+  channels starting at offset = (oy, ox), as the plan reads a pitched tensor or writes the interior of a zero-bordered one; out
+  has x's shape and keeps what out_init holds (default zeros) outside the view.  chunks: row ranges of the statistics pass (0:
+  the launcher's choice).  Returns (out, recorded |max| of out, mean [B,32], var [B,32])."""
+  lib = _L(lib)
+  x = f32(x); gamma = f32(gamma); beta = f32(beta)
+  B, Ha, Wa, ldc = x.shape
+  h, w, C = (Ha, Wa, ldc) if view is None else view
+  oy, ox = offset
+  assert gamma.shape == (C,) and beta.shape == (C,)
+  mode, rH, rW, rp = 0, 0, 0, None
+  if res is not None:
+    res = f32(res)
+    mode = 2 if upsample else 1
+    rH, rW = res.shape[1:3]
+    assert res.shape == (B, rH, rW, C)
+    rp = fptr(res)
+  out = np.zeros(x.shape, np.float32) if out_init is None else f32(out_init).copy()
+  assert out.shape == x.shape
+  amax = np.zeros(1, np.float32); mean = np.empty((B, 32), np.float32); var = np.empty((B, 32), np.float32)
+  lib.check(lib.dll.odt_op_group_norm(device, fptr(x), B, Ha, Wa, ldc, int(h), int(w), int(C), int(oy), int(ox), fptr(gamma), fptr(beta),
+                                      float(eps), int(bool(relu)), mode, rp, int(rH), int(rW), int(chunks), fptr(out), fptr(amax),
+                                      fptr(mean), fptr(var)))
+  return out, float(amax[0]), mean, var
+
+
 def se_tail(t2, w3, b3, fc1, fc2, shortcut, lib=None, device=0):
   """The tail of an SE bottleneck (reference nn.py:502-521) as the plan runs it: pool of t2 [B,H,W,ch] -> gate (conv3 + BN
   folded into fc1 = (W [4 ch, ch / 4], b), fc2 = (W [ch / 4, 4 ch], b)) -> conv3 (w3 [ch, 4 ch] with BN folded, + b3) ->

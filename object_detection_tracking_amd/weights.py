@@ -42,6 +42,26 @@ def deformable_groups(config):
   return [g for g in (1, 2, 3) if 1 <= config.resnet_num_block[g] <= 3]
 
 
+def group_norm_scopes(config):
+  """The GroupNorm scopes of a --use_gn graph in execution order (reference nn.py:81-108, 859-862, 987-1009): X/gn behind every
+  backbone conv X that carries X/bn without the flag, fpn/gn_cN behind the lateral and fpn/gn_pN behind the posthoc convs.
+  [] without the flag."""
+  if not getattr(config, "use_gn", False):
+    return []
+  out = []
+  for scope, _, _, _, has_bn, _ in backbone_conv_specs(config):
+    if has_bn:
+      out.append(scope + "/gn")
+    elif scope.startswith("fpn/lateral_1x1_") or scope.startswith("fpn/posthoc_3x3_"):
+      out.append("fpn/gn_" + scope[16:])
+  return out
+
+
+def group_norm_variables(config):
+  """Names of the gamma / beta variables a --use_gn graph needs, in execution order."""
+  return [s + "/" + v for s in group_norm_scopes(config) for v in ("gamma", "beta")]
+
+
 def backbone_conv_specs(config):
   """Yield (scope, kh, cin, cout, has_bn, has_bias) for every conv on the path,
   in execution order (reference nn.py:843-1014, models.py:979-1009); cin is W's third dimension -- the channels per
@@ -100,6 +120,8 @@ def synthetic_weights(config, seed=0):
   # a deformable block's conv2 has no BN (nn.py:483-485): its four draws are made and dropped, so that every other variable
   # stays bit-identical to the weights of the same seed without the flag
   bn_less = {"group%d/block0/conv2" % g for g in deformable_groups(config)}
+  # --use_gn: likewise every BN draw is made and dropped; the gn/{gamma,beta} variables come from a generator of their own
+  use_gn = bool(getattr(config, "use_gn", False))
 
   def normal(shape, std):
     return (rng.standard_normal(shape, dtype=np.float32) * np.float32(std))
@@ -129,7 +151,7 @@ def synthetic_weights(config, seed=0):
       bn[scope + "/bn/mean/EMA"] = normal((cout,), 0.05)
       bn[scope + "/bn/variance/EMA"] = rng.uniform(0.8, 1.2, cout).astype(
           np.float32)
-      if has_bn:
+      if has_bn and not use_gn:
         w.update(bn)
   dim = config.fpn_frcnn_fc_head_dim
   ch = config.fpn_num_channel
@@ -180,6 +202,19 @@ def synthetic_weights(config, seed=0):
       pre = "group%d/block0/conv2_offset" % g
       w[pre + "/W"] = d_rng.standard_normal((3, 3, C, 18), dtype=np.float32) * np.float32(1.5 * np.sqrt(1.0 / (9 * C)))
       w[pre + "/b"] = d_rng.standard_normal((18,), dtype=np.float32) * np.float32(0.5)
+  if use_gn:
+    # --use_gn (nn.py:81-108): gamma ~ U[0.9, 1.1], beta ~ N(0, 0.02); a block's last norm (conv3/gn) scaled by 0.25, so that the
+    # residual branch neither vanishes nor swamps the shortcut behind a normalisation to unit variance
+    g_rng = np.random.default_rng([seed, 8])
+    chans = {s: c for s, _, _, c, _, _ in backbone_conv_specs(config)}
+    for scope in group_norm_scopes(config):
+      conv = scope[:-3] if scope.endswith("/gn") else ("fpn/lateral_1x1_" if scope[7] == "c" else "fpn/posthoc_3x3_") + scope[7:]
+      C = chans[conv]
+      gamma = g_rng.uniform(0.9, 1.1, C).astype(np.float32)
+      if scope.endswith("/conv3/gn"):
+        gamma *= np.float32(0.25)
+      w[scope + "/gamma"] = gamma
+      w[scope + "/beta"] = g_rng.standard_normal(C, dtype=np.float32) * np.float32(0.02)
   return w
 
 

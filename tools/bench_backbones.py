@@ -15,6 +15,11 @@ python tools/bench_backbones.py --backbones r101_nodil,r101_deformable
   Only these, in this order, in one run: profiles/backbones_deformable_b8_1080p.txt.
 python tools/bench_backbones.py --only resnext101 --steps 3
   Just that handle in this process: the program to put behind `rocprofv3 --kernel-trace --stats --` for per-kernel times.
+python tools/bench_backbones.py --backbones r101,r50_gn,r101_gn
+  The GroupNorm detectors (--use_gn) beside the BatchNorm R101, in one run: profiles/backbones_gn_b8_1080p.txt.  A profiled pass
+  times the GroupNorm launches (csrc/group_norm.hip: statistics, finalize, apply per layer) and prints their share of the step
+  next to the byte floor that describe() computes from the plan's own tensors -- every layer reads its conv output twice and
+  writes it once, the block tails and the FPN sums read a residual on top -- over the measured copy rate.
 One JSON line per backbone, and one with all of them at the end."""
 import argparse, json, os, subprocess, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,7 +28,8 @@ import numpy as np
 COPY_RATE = 6.29e12      # bytes/s, the project's measured device copy rate
 F32_MFMA_RATE = 155e12   # FLOP/s, v_mfma_f32_16x16x4_f32 back to back on every SIMD
 BACKBONES = {"r101": {}, "resnext101": dict(use_resnext=True), "resnet34": dict(resnet34=True), "resnet18": dict(resnet18=True),
-             "r101_nodil": dict(use_dilations=False), "r101_deformable": dict(use_dilations=False, use_deformable=True)}
+             "r101_nodil": dict(use_dilations=False), "r101_deformable": dict(use_dilations=False, use_deformable=True),
+             "r50_gn": dict(resnet50=True, use_gn=True), "r101_gn": dict(use_gn=True)}
 DEFAULT = ("r101", "resnext101", "resnet34", "resnet18")   # what a run without --backbones measures (profiles/backbones_b8_1080p.txt)
 
 
@@ -115,6 +121,14 @@ def child(a, name):
     res["deform_conv"] = {"offset_ms_per_step": dp["deform_offset_profiled_ms"] / n, "conv_ms_per_step": dp["deform_conv_profiled_ms"] / n,
                           "output_pixels": px, "flop_per_step": fl, "offset_flop_per_step": sum(2.0 * B * ho * wo * 9 * C * 18 for C, ho, wo in shapes),
                           "floor_ms_flop_over_f32_mfma_rate": fl / F32_MFMA_RATE * 1e3}
+  if d.get("group_norms", 0) > 0:
+    e.profile(True)
+    run(a.steps)
+    dp = e.describe()
+    e.profile(False)
+    per_fwd = dp["group_norm_profiled_ms"] / max(1, dp["profiled_forwards"])
+    res["group_norm"] = {"layers": d["group_norms"], "ms_per_step": per_fwd, "share_of_step": per_fwd / res["step_ms"],
+                         "bytes_per_step": d["group_norm_floor_bytes"], "floor_ms_bytes_over_copy_rate": d["group_norm_floor_bytes"] / COPY_RATE * 1e3}
   m.close()
   print(json.dumps(res), flush=True)
   return res
@@ -163,6 +177,11 @@ def main():
       print("            deformable conv2: %.3f ms/step measured (+ conv2_offset %.3f ms);  floor from the shape: %.1f GFLOP -> %.3f ms "
             "at %.0f TF" % (g["conv_ms_per_step"], g["offset_ms_per_step"], g["flop_per_step"] / 1e9, g["floor_ms_flop_over_f32_mfma_rate"],
             F32_MFMA_RATE / 1e12))
+    if "group_norm" in res:
+      g = res["group_norm"]
+      print("            GroupNorm: %d layers, %.3f ms/step measured in a profiled pass (%.0f %% of the step);  floor from the plan's tensors: "
+            "%.1f GB -> %.3f ms at %.2f TB/s" % (g["layers"], g["ms_per_step"], 100.0 * g["share_of_step"], g["bytes_per_step"] / 1e9,
+            g["floor_ms_bytes_over_copy_rate"], COPY_RATE / 1e12))
   print(json.dumps(out), flush=True)
 
 
