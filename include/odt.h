@@ -120,6 +120,13 @@ typedef struct odt_config {
                              * -- and behind every FPN lateral and posthoc conv (fpn/gn_cN, fpn/gn_pN; nn.py:987-1009).  Nothing is folded
                              * into the conv weights: each normalised conv is followed by the launches of csrc/group_norm.hip, which carry its
                              * ReLU / residual / top-down add.  block_kind 0 without use_se and use_deformable only */
+  int32_t use_conv_frcnn_head; /* --use_conv_frcnn_head (fastrcnn 4conv1fc; conv_frcnn_head, models.py:1110-1124): the box head runs four
+                             * 3x3 'SAME' convs + ReLU over the [R,7,7,fpn_channels] RoI features -- variables fastrcnn/conv{0..3}/{W
+                             * [3,3,cin,conv_head_dim], b} -- then ONE dense layer fastrcnn/fc/{W [conv_head_dim * 49, head_dim], b} + ReLU
+                             * in place of fc6 / fc7; the fastrcnn/outputs layers follow unchanged.  With use_gn each conv's ReLU is
+                             * followed by GroupNorm per RoI (fastrcnn/gn{0..3}/{gamma,beta}; csrc/group_norm_roi.hip: one launch, one
+                             * pass) with nothing behind it.  Any backbone; with or without add_mask */
+  int32_t conv_head_dim;    /* conv_frcnn_head_dim (256): channels of the four head convs; a multiple of 32 in [32, 512] */
 } odt_config;
 
 /* conv_arith: all modes keep f32 tensors and f32 accumulation.  ODT_ARITH_F32: every product on the exact-f32 MFMA
@@ -544,6 +551,12 @@ int odt_op_deform_conv_view(int device, const float* x, int B, int Ha, int Wa, i
 int odt_op_group_norm(int device, const float* x, int B, int Ha, int Wa, int ldc, int h, int w, int C, int oy, int ox,
                       const float* gamma, const float* beta, float eps, int relu, int res_mode, const float* res, int res_H,
                       int res_W, int chunks, float* out, float* amax, float* mean, float* var);
+/* GroupNorm of RoI tensors (csrc/group_norm_roi.hip; the 4-conv box head under --use_gn) as the plan runs it: x is [R,h,w,ldc] (ldc % 4
+ * == 0, h * w <= 64) and the op normalises the C channels (C % 32 == 0, 32 <= C <= 512) of every RoI with the arithmetic of
+ * odt_op_group_norm, in one launch and one pass; no residual, no activation.  out has x's geometry and comes back as it went in past
+ * channel C.  amax [1]: the |max| the kernel recorded for out; mean, var [R,32]. */
+int odt_op_group_norm_roi(int device, const float* x, int R, int h, int w, int ldc, int C, const float* gamma, const float* beta,
+                          float eps, float* out, float* amax, float* mean, float* var);
 /* BiFPN node input fusion (launch_bifpn_fuse): n = 1..3 inputs ins[k] [B,in_hw[k][0],in_hw[k][1],ldc], mode[k] 0 same
  * size, 1 nearest resize, 2 3x3 / s2 'SAME' max pool with pads[k] = (top, left); wsm != NULL: 'fastattn' with the raw
  * WSM scalars [n], else a plain sum; act 0 / 2 (swish).  out [B,h,w,ldc]. */

@@ -105,6 +105,7 @@ def finalize_config(c):
   c.fpn_num_channel = 256
   c.fpn_frcnn_fc_head_dim = 1024
   d.setdefault("mrcnn_head_dim", 256)          # obj_detect_tracking.py:324
+  d.setdefault("conv_frcnn_head_dim", 256)     # main.py:250 (the inference driver never sets it); --use_conv_frcnn_head
   # backbone depth flags (obj_detect_tracking.py:188-191, 348-359): a set flag decides the block counts and the block
   # function, as there; without one a given resnet_num_block / use_basic_block stands (R101 bottlenecks by default)
   d.setdefault("resnet_num_block", [3, 4, 23, 3])

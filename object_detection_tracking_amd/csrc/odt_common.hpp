@@ -490,6 +490,22 @@ int group_norm_chunks(int h, int w, int C);
 int group_norm_parts(int h, int w, int C, int chunks);      // partials per (image, group) that a launch with these sizes writes
 int launch_group_norm(const GroupNormParams& p, hipStream_t stream);
 
+// ------------------------------------------------------- GroupNorm of ROI tensors (group_norm_roi.hip; --use_gn + --use_conv_frcnn_head)
+// The same arithmetic per ROI and group over the hw <= 64 pixels of x [R, hw, ldc], in one launch and one pass: no residual, no
+// activation, no scratch.  32 <= C <= 512, C % 32 == 0; ldc, out_ldc multiples of 4; every pointer 16-byte aligned.
+struct RoiGroupNormParams {
+  const float* x;       // [R, hw, ldc]
+  const float* gamma;   // [C]
+  const float* beta;    // [C]
+  float* out;           // [R, hw, out_ldc]; channels past C are not written.  May be x
+  float* mean;          // [R][32] or nullptr
+  float* var;           // [R][32] or nullptr
+  unsigned* amax;       // range slot of out (|max| of what is stored) or nullptr
+  int R, hw, C, ldc, out_ldc;
+  float eps;
+};
+int launch_group_norm_roi(const RoiGroupNormParams& p, hipStream_t stream);
+
 // ------------------------------------------------------- EfficientDet tail (effdet_post.hip)
 struct EffPostParams {
   const float* cls[5];     // per level [B, npix, ldc_cls]  (9 * ncls valid channels: anchor-major)

@@ -60,13 +60,14 @@ struct ConvOp {
 
 enum OpKind { OP_PRE, OP_CONV, OP_POOL, OP_SUB2, OP_PROPOSALS, OP_ROI_HEAD, OP_DETECT, OP_ROI_FINAL,
               OP_ROI_MASK, OP_MASK_SELECT, OP_PRE_RGB, OP_DW, OP_CMEAN, OP_CSCALE, OP_FUSE, OP_EFF_POST, OP_ROI_EFF, OP_SE_GATE,
-              OP_SE_GATE_MEAN, OP_WSCALE, OP_MB_EXPAND_DW, OP_RSE_GATE, OP_RSE_APPLY, OP_GCONV, OP_BLOCK, OP_DCONV, OP_GN };
+              OP_SE_GATE_MEAN, OP_WSCALE, OP_MB_EXPAND_DW, OP_RSE_GATE, OP_RSE_APPLY, OP_GCONV, OP_BLOCK, OP_DCONV, OP_GN, OP_GN_ROI };
 struct Op {
   OpKind kind;
   int conv = -1;        // index into convs (OP_BLOCK: the block's conv2, whose record launches conv_block_kernel)
   int gconv = -1;       // OP_GCONV: its index among the plan's grouped convs (profiling events)
   int dconv = -1;       // OP_DCONV: its index among the plan's deformable convs (profiling events)
   int gnorm = -1;       // OP_GN: its index among the plan's GroupNorm layers (profiling events)
+  int gnroi = -1;       // OP_GN_ROI: its index among the plan's ROI GroupNorm layers (profiling events)
   Tensor in, out;
   DwConvParams dw{};    // OP_DW
   MbExpandDwParams mb{};   // OP_MB_EXPAND_DW
@@ -77,6 +78,7 @@ struct Op {
   GroupConvParams gc{};    // OP_GCONV: the ResNeXt block's 32-group 3x3 conv2 (conv_group.hip)
   DeformConvParams dc{};   // OP_DCONV: a deformable stage entry's conv2_offset + deformable conv2 (conv_deform.hip)
   GroupNormParams gn{};    // OP_GN: GroupNorm of a conv's output + what that conv's epilogue would have carried (group_norm.hip)
+  RoiGroupNormParams gnr{};   // OP_GN_ROI: GroupNorm behind a conv of the 4-conv box head, per ROI (group_norm_roi.hip)
   float* aux = nullptr; // OP_CMEAN: means out [B,ldc]; OP_CSCALE / OP_WSCALE: gates in [B,ldc]
   const float* wt0 = nullptr;   // OP_WSCALE: the conv's unscaled weights [Cout][K] (conv = index of the conv whose weights are rebuilt)
   float* aux2 = nullptr;   // OP_CMEAN: partial-sum scratch
@@ -137,6 +139,7 @@ struct odt_model {
   int gconv_ops = 0;                 // ResNeXt (odt_config.block_kind == 2): launches of the 32-group 3x3 conv per forward (conv_group.hip)
   int dconv_ops = 0;                 // odt_config.use_deformable: stage entries that run conv2_offset + the deformable conv2 (conv_deform.hip)
   int gn_ops = 0;                    // odt_config.use_gn: GroupNorm layers, three launches each (group_norm.hip)
+  int gn_roi_ops = 0;                // odt_config.use_gn + use_conv_frcnn_head: ROI GroupNorm layers of the box head, one launch each (group_norm_roi.hip)
   int mb_fused = 0;                  // EfficientNet: MBConv blocks whose expand + depthwise run as one kernel (effnet_mbconv.hip)
   // tail overlap: the selection / ROIAlign / box-head / NMS kernels of forward i (a few dozen workgroups each,
   // ~2 ms per 8-frame step) run on a side stream under the backbone of forward i+1.  The next forward's FPN stage
@@ -187,6 +190,8 @@ struct odt_model {
   double prof_doff_ms = 0, prof_dconv_ms = 0;
   std::vector<hipEvent_t> ev_gn;     // OP_GN i: events [2 i, 2 i + 1]
   double prof_gn_ms = 0;
+  std::vector<hipEvent_t> ev_gn_roi; // OP_GN_ROI i: events [2 i, 2 i + 1]
+  double prof_gn_roi_ms = 0;
   int prof_forwards = 0;
   int prof_launches = 0;
 
@@ -317,6 +322,7 @@ void visit_op_ptrs(odt_model* m, size_t oi, F&& f) {
     case OP_DCONV: f(op.dc.in); f(op.dc.off); f(op.dc.out); break;
     // (part / ab / mean / var are dedicated allocations shared by the plan's GroupNorm layers: attach_group_norm_scratch)
     case OP_GN: f(op.gn.x); f(op.gn.res); f(op.gn.out); break;
+    case OP_GN_ROI: f(op.gnr.x); f(op.gnr.out); break;      // (mean / var, where kept, are dedicated allocations)
     case OP_FUSE: for (auto& p : op.fuse.in) f(p); f(op.fuse.out); break;
     case OP_EFF_POST: for (auto& p : m->eff_post.cls) f(p); for (auto& p : m->eff_post.box) f(p); break;
     case OP_CMEAN: case OP_CSCALE: case OP_SE_GATE: case OP_SE_GATE_MEAN: case OP_WSCALE: case OP_POOL: case OP_SUB2: break;

@@ -1120,6 +1120,29 @@ int odt_op_group_norm(int device, const float* x, int B, int Ha, int Wa, int ldc
   return get_dev(out, dout, n);
 }
 
+int odt_op_group_norm_roi(int device, const float* x, int R, int h, int w, int ldc, int C, const float* gamma, const float* beta,
+                          float eps, float* out, float* amax, float* mean, float* var) {
+  ODT_CHECK(x && gamma && beta && out && amax && mean && var, "odt_op_group_norm_roi: null argument");
+  ODT_CHECK(R >= 1 && h >= 1 && w >= 1 && ldc >= 1 && C >= 1 && (double)R * h * w * ldc < 1073741824.0, "odt_op_group_norm_roi: bad sizes");
+  if (set_dev(device)) return 1;
+  GBufs g;
+  RoiGroupNormParams p; std::memset(&p, 0, sizeof(p));
+  const size_t n = (size_t)R * h * w * ldc;
+  float *dx, *dg, *db, *dout;
+  unsigned* slot;
+  // (out starts as a copy of the caller's buffer: the pad channels must come back as they went in)
+  if (g.alloc("x", n, &dx, -1, x) || g.alloc("gamma", (size_t)C, &dg, -1, gamma) || g.alloc("beta", (size_t)C, &db, -1, beta) ||
+      g.alloc("out", n, &dout, -1, out) || g.alloc("range slot", (size_t)kAmaxWays, &slot, 0) ||
+      g.alloc("mean", (size_t)R * kGnGroups, &p.mean) || g.alloc("var", (size_t)R * kGnGroups, &p.var)) return 1;
+  p.x = dx; p.gamma = dg; p.beta = db; p.out = dout; p.amax = slot;
+  p.R = R; p.hw = h * w; p.C = C; p.ldc = ldc; p.out_ldc = ldc; p.eps = eps;
+  if (launch_group_norm_roi(p, nullptr)) return 1;
+  if (g.check("odt_op_group_norm_roi")) return 1;
+  if (rse_read_amax(slot, amax)) return 1;
+  if (get_dev(mean, p.mean, (size_t)R * kGnGroups) || get_dev(var, p.var, (size_t)R * kGnGroups)) return 1;
+  return get_dev(out, dout, n);
+}
+
 int odt_op_effdet_post(int device, int B, int ncls, const int32_t* npix, int ldc_cls, int ldc_box,
                        const float* const* cls, const float* const* box, const float* anchors, int k, int max_out,
                        float score_thresh, float iou_thresh, float image_scale, int32_t* cand_idx, float* cand_boxes,

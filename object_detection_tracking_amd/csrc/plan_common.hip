@@ -388,6 +388,20 @@ int attach_split_weights(odt_model* m) {
       if (m->range_slot_name[slot].empty()) m->range_slot_name[slot] = "GroupNorm output";
       continue;
     }
+    if (op.kind == OP_GN_ROI) {
+      // a ROI GroupNorm of the 4-conv box head, likewise: the next head conv and the fc read its output
+      slot_of.erase(op.gnr.out);
+      if (pol.family != 2) continue;
+      const int g = tail ? 1 : 0;
+      ODT_CHECK(m->amax_used[g] < odt_model::kAmaxSlots, "too many conv outputs for the range slots");
+      const int slot = (tail ? odt_model::kAmaxSlots : 0) + m->amax_used[g]++;
+      slot_of[op.gnr.out] = slot;
+      m->ops[oi].gnr.amax = m->amax_dev + (size_t)slot * kAmaxWays;
+      for (const auto& kv : m->taps)
+        if (kv.second.d == op.gnr.out) m->range_slot_name[slot] = kv.first + " (ROI GroupNorm)";
+      if (m->range_slot_name[slot].empty()) m->range_slot_name[slot] = "ROI GroupNorm output";
+      continue;
+    }
     if (op.kind == OP_POOL || op.kind == OP_SUB2) {
       auto it = slot_of.find(op.in.d);
       if (it != slot_of.end()) slot_of[op.out.d] = it->second; else slot_of.erase(op.out.d);

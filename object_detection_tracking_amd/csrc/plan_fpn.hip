@@ -59,6 +59,36 @@ int add_group_norm(odt_model* m, const std::string& scope, const Tensor& y, int 
   return 0;
 }
 
+// Append GroupNorm per ROI of y [R,7,7,C] over scope/{gamma,beta} (the 4-conv box head under use_gn: behind the conv's ReLU,
+// nothing behind it): one launch of group_norm_roi.hip, out of place like add_group_norm.  Not counted among the frame-level
+// layers (gn_ops).  keep_taps handles expose the statistics of fastrcnn/gn0 as "head_conv0/gn_mean" / "head_conv0/gn_var" [R,32]
+int add_group_norm_roi(odt_model* m, const std::string& scope, const Tensor& y, const std::string& tap, Tensor* out) {
+  const int C = y.c;
+  ODT_CHECK(C % kGnGroups == 0, "GroupNorm: " + scope + " has " + std::to_string(C) + " channels, not a multiple of 32");
+  ODT_CHECK(y.H == y.h && y.W == y.w, "GroupNorm: the ROI tensor in front of " + scope + " is not dense");
+  const HostTensor* g = find_w(m, scope + "/gamma");
+  const HostTensor* b = find_w(m, scope + "/beta");
+  ODT_CHECK(g && b, "missing GroupNorm variables " + scope + "/{gamma,beta} (odt_config.use_gn with use_conv_frcnn_head)");
+  ODT_CHECK(g->data.size() == (size_t)C && b->data.size() == (size_t)C, "bad GroupNorm shapes for " + scope);
+  if (make_tensor(m, tap, y.B, y.H, y.W, C, out)) return 1;
+  Op op; op.kind = OP_GN_ROI; op.out = *out;
+  RoiGroupNormParams& p = op.gnr;
+  std::memset(&p, 0, sizeof(p));
+  if (upload_raw(m, g->data, &p.gamma) || upload_raw(m, b->data, &p.beta)) return 1;
+  p.x = y.d; p.out = out->d;
+  p.R = y.B; p.hw = y.h * y.w; p.C = C; p.ldc = y.C; p.out_ldc = out->C; p.eps = 1e-5f;
+  if (m->cfg.keep_taps && scope == "fastrcnn/gn0") {
+    p.mean = m->alloc_f((size_t)y.B * kGnGroups, true); p.var = m->alloc_f((size_t)y.B * kGnGroups, true);
+    ODT_CHECK(p.mean && p.var, "device allocation failed (GroupNorm statistics of " + scope + ")");
+    Tensor t{}; t.B = 1; t.H = t.h = 1; t.W = t.w = y.B; t.C = t.c = kGnGroups;
+    t.d = p.mean; m->taps[tap + "/gn_mean"] = t;
+    t.d = p.var; m->taps[tap + "/gn_var"] = t;
+  }
+  op.gnroi = m->gn_roi_ops++;
+  m->ops.push_back(op);
+  return 0;
+}
+
 // upload the weights of the scope `c` is named after (W + folded BN where has_bn, W + b otherwise) and append the conv.  Under
 // odt_config.use_gn a normalised layer is the conv as it is -- nothing folded, no activation, residual or offset -- followed by
 // its GroupNorm, which carries them
@@ -439,25 +469,63 @@ int box_head(odt_model* m, const Tensor P[5], const Tensor& props, Tensor* hout)
   m->roi_final = rh;
   { Op op; op.kind = OP_ROI_HEAD; m->ops.push_back(op); }
 
-  {   // fc6: rows of W are flattened NCHW (c*49 + h*7 + w, nn.py:736-738); our RoI rows are (h,w,c)
-    const HostTensor* w6 = find_w(m, "fastrcnn/fc6/W");
-    ODT_CHECK(w6 && w6->data.size() == (size_t)FC * 49 * D, "missing/bad fastrcnn/fc6/W");
+  // the dense layer behind the RoI tensor of `cin` channels: rows of W are flattened NCHW (c*49 + h*7 + w, nn.py:736-738); our
+  // RoI rows are (h,w,c).  scope/{W,b} -> the variables `as`/{W,b}
+  auto flat_dense = [&](const std::string& scope, int cin, const std::string& as) -> int {
+    const HostTensor* w6 = find_w(m, scope + "/W");
+    ODT_CHECK(w6 && w6->data.size() == (size_t)cin * 49 * D, "missing/bad " + scope + "/W");
     HostTensor v; v.data.resize(w6->data.size());
-    for (int c = 0; c < FC; ++c)
+    for (int c = 0; c < cin; ++c)
       for (int s = 0; s < 49; ++s)
-        std::memcpy(&v.data[((size_t)s * FC + c) * D], &w6->data[((size_t)c * 49 + s) * D], sizeof(float) * D);
-    m->host_w["__fc6/W"] = v;
-    const HostTensor* b6 = find_w(m, "fastrcnn/fc6/b"); ODT_CHECK(b6 != nullptr, "missing fastrcnn/fc6/b");
-    m->host_w["__fc6/b"] = *b6;
-  }
+        std::memcpy(&v.data[((size_t)s * cin + c) * D], &w6->data[((size_t)c * 49 + s) * D], sizeof(float) * D);
+    m->host_w[as + "/W"] = v;
+    const HostTensor* b6 = find_w(m, scope + "/b"); ODT_CHECK(b6 != nullptr && b6->data.size() == (size_t)D, "missing/bad " + scope + "/b");
+    m->host_w[as + "/b"] = *b6;
+    return 0;
+  };
   Tensor h6{}, h7{};
   // compacted rows: only the first nprops[b] rows of each image are meaningful
-  ConvSpec c6("fastrcnn/fc6", roi, 49 * FC, D);
-  c6.relu = 1; c6.tap = "fc6";
-  if (upload_conv(m, "__fc6", 1, 1, 49 * FC, D, false, &c6.wt, &c6.bias) || add_conv(m, c6, &h6)) return 1;
-  ConvSpec c7("fastrcnn/fc7", h6, D, D);
-  c7.relu = 1; c7.tap = "fc7";
-  if (conv_layer(m, c7, false, &h7)) return 1;
+  if (cfg.use_conv_frcnn_head) {
+    // --use_conv_frcnn_head (fastrcnn 4conv1fc: conv_frcnn_head, models.py:1110-1124, from :1038-1041 / :1133-1136 /
+    // :2656-2659): four 3x3 'SAME' convs with ReLU over the [R,7,7,FC] RoI images -- under use_gn each followed by GroupNorm,
+    // BEHIND the ReLU and with no activation of its own -- then ONE dense layer fastrcnn/fc + ReLU; no fc6 / fc7.  Rows past
+    // nprops[b] are zero RoIs: finite through every layer, normalised like any other row
+    const int DC = cfg.conv_head_dim, R = B * K;
+    ODT_CHECK(DC >= 32 && DC <= 512 && DC % 32 == 0, "use_conv_frcnn_head: odt_config.conv_head_dim must be a multiple of 32 in [32, 512]");
+    Tensor cur = roi;
+    cur.B = R; cur.H = cur.h = kRoiOut; cur.W = cur.w = kRoiOut; cur.C = cur.c = FC;
+    for (int k = 0; k < 4; ++k) {
+      const std::string ks = std::to_string(k), scope = "fastrcnn/conv" + ks;
+      const int cin = k == 0 ? FC : DC;
+      const HostTensor* w = find_w(m, scope + "/W"); const HostTensor* b = find_w(m, scope + "/b");
+      ODT_CHECK(w && b, "missing 4-conv box head variables " + scope + "/{W,b} (odt_config.use_conv_frcnn_head)");
+      ODT_CHECK(w->data.size() == (size_t)9 * cin * DC && b->data.size() == (size_t)DC,
+                "bad shapes for " + scope + " (W [3,3," + std::to_string(cin) + "," + std::to_string(DC) + "], b [" + std::to_string(DC) + "])");
+      ConvSpec c(scope, cur, cin, DC);
+      c.kh = c.kw = 3; c.pad_t = c.pad_l = 1; c.relu = 1;
+      c.tap = cfg.use_gn ? "" : "head_conv" + ks;
+      Tensor y{}, nx{};
+      if (conv_layer(m, c, false, &y)) return 1;
+      if (!cfg.use_gn) nx = y;
+      else if (add_group_norm_roi(m, "fastrcnn/gn" + ks, y, "head_conv" + ks, &nx)) return 1;
+      cur = nx;
+    }
+    ODT_CHECK(cur.C == DC && cur.H == kRoiOut && cur.W == kRoiOut, "4-conv box head: the last conv's output is not dense");
+    Tensor flat = cur;                    // [R,7,7,DC] viewed as [1,1,R,49*DC]
+    flat.B = 1; flat.H = flat.h = 1; flat.W = flat.w = R; flat.C = flat.c = 49 * DC;
+    if (flat_dense("fastrcnn/fc", DC, "__headfc")) return 1;
+    ConvSpec cf("fastrcnn/fc", flat, 49 * DC, D);
+    cf.relu = 1; cf.tap = "head_fc";
+    if (upload_conv(m, "__headfc", 1, 1, 49 * DC, D, false, &cf.wt, &cf.bias) || add_conv(m, cf, &h7)) return 1;
+  } else {
+    if (flat_dense("fastrcnn/fc6", FC, "__fc6")) return 1;
+    ConvSpec c6("fastrcnn/fc6", roi, 49 * FC, D);
+    c6.relu = 1; c6.tap = "fc6";
+    if (upload_conv(m, "__fc6", 1, 1, 49 * FC, D, false, &c6.wt, &c6.bias) || add_conv(m, c6, &h6)) return 1;
+    ConvSpec c7("fastrcnn/fc7", h6, D, D);
+    c7.relu = 1; c7.tap = "fc7";
+    if (conv_layer(m, c7, false, &h7)) return 1;
+  }
   if (concat_cout(m, "fastrcnn/outputs/class", C, "fastrcnn/outputs/box", 4 * C, D, "__headout")) return 1;
   ConvSpec co("fastrcnn/outputs", h7, D, C * 5);
   co.out_ldc = (C * 5 + 3) / 4 * 4; co.tap = "head_out";

@@ -148,6 +148,11 @@ static int run_ops(odt_model* m, const void* src, int dtype, hipStream_t st, siz
         if (launch_group_norm(op.gn, st)) return 1;
         if (m->profile) ODT_HIP(hipEventRecord(m->ev_gn[2 * op.gnorm + 1], st));
         break;
+      case OP_GN_ROI:             // --use_gn + --use_conv_frcnn_head: one launch behind a conv of the box head
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_gn_roi[2 * op.gnroi], st));
+        if (launch_group_norm_roi(op.gnr, st)) return 1;
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_gn_roi[2 * op.gnroi + 1], st));
+        break;
       case OP_MASK_SELECT:
         if (launch_mask_select(m->mask_sel, st)) return 1;
         break;
@@ -229,6 +234,11 @@ static int finish_profile(odt_model* m, hipStream_t st) {
     ODT_HIP(hipEventElapsedTime(&t, m->ev_gn[2 * i], m->ev_gn[2 * i + 1]));
     m->prof_gn_ms += t;
   }
+  for (int i = 0; i < m->gn_roi_ops; ++i) {
+    float t = 0;
+    ODT_HIP(hipEventElapsedTime(&t, m->ev_gn_roi[2 * i], m->ev_gn_roi[2 * i + 1]));
+    m->prof_gn_roi_ms += t;
+  }
   ++m->prof_forwards;
   float tt = 0;
   ODT_HIP(hipEventElapsedTime(&tt, m->ev_total[0], m->ev_total[1]));
@@ -277,6 +287,7 @@ int run_plan(odt_model* m, const void* frames, int dtype, int on_device, hipStre
     while (m->ev_gconv.size() < 2 * (size_t)m->gconv_ops) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_gconv.push_back(e); }
     while (m->ev_dconv.size() < 3 * (size_t)m->dconv_ops) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_dconv.push_back(e); }
     while (m->ev_gn.size() < 2 * (size_t)m->gn_ops) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_gn.push_back(e); }
+    while (m->ev_gn_roi.size() < 2 * (size_t)m->gn_roi_ops) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_gn_roi.push_back(e); }
     for (int i = 0; i < 2; ++i) if (!m->ev_total[i]) ODT_HIP(hipEventCreate(&m->ev_total[i]));
     ODT_HIP(hipEventRecord(m->ev_total[0], st));
   }
@@ -366,6 +377,7 @@ int odt_destroy(odt_handle h) {
   for (auto e : h->ev_gconv) (void)hipEventDestroy(e);
   for (auto e : h->ev_dconv) (void)hipEventDestroy(e);
   for (auto e : h->ev_gn) (void)hipEventDestroy(e);
+  for (auto e : h->ev_gn_roi) (void)hipEventDestroy(e);
   for (auto e : h->ev_total) if (e) (void)hipEventDestroy(e);
   for (auto& sl : h->slot) {
     if (sl.pin_in) (void)hipHostFree(sl.pin_in);
@@ -720,6 +732,7 @@ int odt_profile_enable(odt_handle h, int enable) {
   h->prof_gconv_ms = 0; h->prof_forwards = 0;
   h->prof_doff_ms = h->prof_dconv_ms = 0;
   h->prof_gn_ms = 0;
+  h->prof_gn_roi_ms = 0;
   h->prof_layer_ms.assign(h->convs.size(), 0.0);
   return 0;
 }
@@ -786,6 +799,10 @@ int odt_describe(odt_handle h, char* buf, int cap) {
     const double t = 4.0 * g.B * g.h * g.w * g.C;
     gn_bytes += 3.0 * t + (g.res_mode == 1 ? t : (g.res_mode == 2 ? 4.0 * g.B * ((g.h + 1) / 2) * ((g.w + 1) / 2) * g.C : 0.0));
   }
+  // ... and of the box head's ROI GroupNorms, one pass each: one read and one write
+  double gn_roi_bytes = 0.0;
+  for (const Op& op : h->ops)
+    if (op.kind == OP_GN_ROI) gn_roi_bytes += 8.0 * op.gnr.R * op.gnr.hw * op.gnr.C;
   char tmp[8192];
   std::snprintf(tmp, sizeof(tmp),
                 "{\"conv_arith\": \"%s\", \"conv_launches\": %d, \"convs_fused_into_epilogues\": %d, \"exact_f32_mfma_launches\": %d, "
@@ -797,7 +814,8 @@ int odt_describe(odt_handle h, char* buf, int cap) {
                 "\"use_se\": %d, \"se_blocks\": %d, \"se_blocks_conv1_on_fp16x2\": %d, \"block_kind\": \"%s\", \"group_conv_launches\": %d, "
                 "\"group_conv_profiled_ms\": %.6f, \"profiled_forwards\": %d, \"use_deformable\": %d, \"deform_conv_launches\": %d, "
                 "\"deform_offset_profiled_ms\": %.6f, \"deform_conv_profiled_ms\": %.6f, \"use_gn\": %d, \"group_norms\": %d, "
-                "\"group_norm_profiled_ms\": %.6f, \"group_norm_floor_bytes\": %.0f}",
+                "\"group_norm_profiled_ms\": %.6f, \"group_norm_floor_bytes\": %.0f, \"box_head\": \"%s\", \"roi_group_norms\": %d, "
+                "\"roi_group_norm_profiled_ms\": %.6f, \"roi_group_norm_floor_bytes\": %.0f}",
                 h->policy.arith != 0 && fam[2] > 0 ? "f32 through fp16x2 / bf16x3 split products"
                     : (h->policy.arith != 0 && fam[1] + fam[3] > 0 ? "f32 through bf16x3 split products" : "exact f32 MFMA"),
                 (int)h->convs.size() - nfused, nfused, fam[0], fam[1] + fam[3], fam[2], h->convs_h2f, h->blocks_fused, h->stem_fused, h->mb_fused, fam[3], fam[1], fam[2], nsk, h->policy.family,
@@ -806,7 +824,8 @@ int odt_describe(odt_handle h, char* buf, int cap) {
                 h->dedicated_tensor_bytes, h->cfg.keep_taps, h->chunked_convs, h->cfg.use_se != 0 ? 1 : 0, h->se_blocks, se_conv1_h2,
                 h->cfg.block_kind == 1 ? "basic" : (h->cfg.block_kind == 2 ? "resnext32x4d" : "bottleneck"), h->gconv_ops,
                 h->prof_gconv_ms, h->prof_forwards, h->cfg.use_deformable != 0 ? 1 : 0, h->dconv_ops, h->prof_doff_ms, h->prof_dconv_ms,
-                h->cfg.use_gn != 0 ? 1 : 0, h->gn_ops, h->prof_gn_ms, gn_bytes);
+                h->cfg.use_gn != 0 ? 1 : 0, h->gn_ops, h->prof_gn_ms, gn_bytes,
+                h->cfg.graph != ODT_GRAPH_EFFNET && h->cfg.use_conv_frcnn_head != 0 ? "4conv1fc" : "2fc", h->gn_roi_ops, h->prof_gn_roi_ms, gn_roi_bytes);
   ODT_CHECK((int)std::strlen(tmp) < cap, "odt_describe: buffer too small");
   std::strncpy(buf, tmp, cap - 1); buf[cap - 1] = 0;
   return 0;

@@ -33,7 +33,7 @@ from .nn import get_new_hw
 from .range_guard import RangeGuard
 from .frozen_pb import load_frozen_pb
 from .tf_checkpoint import load_checkpoint
-from .weights import (backbone_block_kind, deformable_groups, expand_class_agnostic_box, group_norm_variables, load_npz,
+from .weights import (backbone_block_kind, conv_head_variables, deformable_groups, expand_class_agnostic_box, group_norm_variables, load_npz,
                       select_partial_classes)
 
 
@@ -136,6 +136,8 @@ class _Engine(object):
     c.block_kind = backbone_block_kind(config)                  # include/odt.h: 0 bottleneck | 1 basic | 2 ResNeXt-32x4d
     c.use_deformable = int(bool(getattr(config, "use_deformable", False)))      # deformable conv2 in the stage-entry bottlenecks
     c.use_gn = int(bool(getattr(config, "use_gn", False)))      # GroupNorm in the backbone and the FPN
+    c.use_conv_frcnn_head = int(bool(getattr(config, "use_conv_frcnn_head", False)))      # 4 convs + one FC in place of fc6 / fc7
+    c.conv_head_dim = int(getattr(config, "conv_frcnn_head_dim", 256))
     B, P, Cn = batch, self.per_im, self.channels
     self._boxes = np.zeros((B, P, 4), np.float32)
     self._probs = np.zeros((B, P), np.float32)
@@ -391,15 +393,14 @@ class _DetectorBase(object):
         raise ValueError("weights: pass a {name: array} dict or set config.model_path to a "
                          "Tensorpack-style .npz (reference obj_detect_tracking.py:417-435), a "
                          "TF checkpoint directory / prefix, or a frozen .pb (--is_load_from_pb)")
-    unsupported = [f for f in ("add_relation_nn",
-                               "use_conv_frcnn_head", "use_att_frcnn_head",
+    unsupported = [f for f in ("add_relation_nn", "use_att_frcnn_head",
                                "use_small_object_head", "use_cascade_rcnn")
                    if getattr(self.config, f, False)]
     if unsupported:
       raise NotImplementedError("graph variants not built on this path (SURVEY.md 8, out of scope): "
                                 + ", ".join(unsupported))
     if getattr(self.config, "use_gn", False):
-      # --use_gn (nn.py:81-108): GroupNorm in the plain bottleneck backbone and the FPN, in front of the 2-FC box head
+      # --use_gn (nn.py:81-108): GroupNorm in the plain bottleneck backbone and the FPN (and, with use_conv_frcnn_head, the box head)
       for f in ("use_se", "use_resnext", "use_basic_block", "use_deformable"):
         if getattr(self.config, f, False):
           raise NotImplementedError("graph variants not built on this path: use_gn together with %s" % f)
@@ -407,6 +408,17 @@ class _DetectorBase(object):
       if missing:
         raise NotImplementedError("a GroupNorm graph cannot be built from weights without gn/{gamma,beta} variables: missing "
                                   + ", ".join(missing[:4]) + (" ... (%d in all)" % len(missing) if len(missing) > 4 else ""))
+    if getattr(self.config, "use_conv_frcnn_head", False):
+      # --use_conv_frcnn_head (models.py:1110-1124): fastrcnn/conv0..3 (+ fastrcnn/gn0..3 under use_gn) and fastrcnn/fc in place
+      # of fc6 / fc7; independent of the backbone, the output layers and the mask head
+      dc = int(getattr(self.config, "conv_frcnn_head_dim", 256))
+      if dc < 32 or dc > 512 or dc % 32 != 0:
+        raise NotImplementedError("graph variants not built on this path: use_conv_frcnn_head with conv_frcnn_head_dim = %d (a "
+                                  "multiple of 32 in [32, 512]: the conv kernels' channel step and GroupNorm's 32 groups)" % dc)
+      missing = [n for n in conv_head_variables(self.config) if n not in weights]
+      if missing:
+        raise NotImplementedError("a 4-conv box head (use_conv_frcnn_head) cannot be built from weights without its variables: "
+                                  "missing " + ", ".join(missing[:4]) + (" ... (%d in all)" % len(missing) if len(missing) > 4 else ""))
     for f in ("use_resnext", "use_basic_block"):
       # the reference's basic and ResNeXt blocks take use_se and ignore it (nn.py:439-456, 524-549): a graph that silently
       # differs from what a --version 6 checkpoint was trained as is worse than an error
@@ -666,7 +678,8 @@ def config_from_weights(weights, add_mask=False, is_multi=False, **overrides):
   overridden.  ``group0/block0/fc1/W`` present means a squeeze-excitation backbone (use_se); unless overridden,
   use_dilations=False follows from it: the only published SE model (version 6) is undilated.  A
   ``groupG/block0/conv2_offset/W`` means deformable stage entries (use_deformable, and no dilations); ``conv0/gn/gamma`` means
-  GroupNorm in the backbone and the FPN (use_gn).  No ``group0/block0/conv3/W``
+  GroupNorm in the backbone and the FPN (use_gn); ``fastrcnn/conv0/W`` means the 4-conv + FC box head (use_conv_frcnn_head, its
+  last axis conv_frcnn_head_dim).  No ``group0/block0/conv3/W``
   means basic blocks (use_basic_block); a ``conv2/W`` of [3,3,C/32,C] means ResNeXt-32x4d (use_resnext)."""
   from .config import make_config
   blocks = [0, 0, 0, 0]
@@ -686,6 +699,8 @@ def config_from_weights(weights, add_mask=False, is_multi=False, **overrides):
     kw.update(use_deformable=True, use_dilations=False)      # (the reference graph does not build with both)
   if "conv0/gn/gamma" in weights:
     kw.update(use_gn=True)                     # GroupNorm variables in place of conv0/bn
+  if "fastrcnn/conv0/W" in weights:            # the 4-conv + FC box head; its width is the conv's Cout
+    kw.update(use_conv_frcnn_head=True, conv_frcnn_head_dim=int(np.asarray(weights["fastrcnn/conv0/W"]).shape[-1]))
   if "group0/block0/conv3/W" not in weights:
     kw.update(use_basic_block=True)            # resnet_basicblock: two 3x3 convs, no conv3
   else:
@@ -695,7 +710,7 @@ def config_from_weights(weights, add_mask=False, is_multi=False, **overrides):
   kw.update(overrides)
   cfg = make_config(**kw)
   cfg.fpn_num_channel = int(np.asarray(weights["fpn/lateral_1x1_c2/W"]).shape[-1])
-  cfg.fpn_frcnn_fc_head_dim = int(np.asarray(weights["fastrcnn/fc6/W"]).shape[-1])
+  cfg.fpn_frcnn_fc_head_dim = int(np.asarray(weights["fastrcnn/fc/W" if cfg.use_conv_frcnn_head else "fastrcnn/fc6/W"]).shape[-1])
   return cfg
 
 

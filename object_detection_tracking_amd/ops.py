@@ -591,6 +591,25 @@ def group_norm(x, gamma, beta, eps=1e-5, relu=False, res=None, upsample=False, v
   return out, float(amax[0]), mean, var
 
 
+def group_norm_roi(x, gamma, beta, eps=1e-5, view=None, out_init=None, lib=None, device=0):
+  """GroupNorm of a RoI tensor as the 4-conv box head runs it under --use_gn (csrc/group_norm_roi.hip): x [R,h,w,C], h * w <= 64,
+  C % 32 == 0 in [32, 512]; per RoI and group of C / 32 adjacent channels the arithmetic of group_norm, in one launch and one
+  pass, with no residual and no activation.  With view = C, x is an allocation [R,h,w,ldc] of which the first C channels are
+  normalised; out has x's shape and keeps what out_init holds (default zeros) past them.  Returns (out, recorded |max| of out,
+  mean [R,32], var [R,32])."""
+  lib = _L(lib)
+  x = f32(x); gamma = f32(gamma); beta = f32(beta)
+  R, h, w, ldc = x.shape
+  C = ldc if view is None else int(view)
+  assert gamma.shape == (C,) and beta.shape == (C,)
+  out = np.zeros(x.shape, np.float32) if out_init is None else f32(out_init).copy()
+  assert out.shape == x.shape
+  amax = np.zeros(1, np.float32); mean = np.empty((R, 32), np.float32); var = np.empty((R, 32), np.float32)
+  lib.check(lib.dll.odt_op_group_norm_roi(device, fptr(x), R, h, w, ldc, C, fptr(gamma), fptr(beta), float(eps), fptr(out), fptr(amax),
+                                          fptr(mean), fptr(var)))
+  return out, float(amax[0]), mean, var
+
+
 def se_tail(t2, w3, b3, fc1, fc2, shortcut, lib=None, device=0):
   """The tail of an SE bottleneck (reference nn.py:502-521) as the plan runs it: pool of t2 [B,H,W,ch] -> gate (conv3 + BN
   folded into fc1 = (W [4 ch, ch / 4], b), fc2 = (W [ch / 4, 4 ch], b)) -> conv3 (w3 [ch, 4 ch] with BN folded, + b3) ->

@@ -62,6 +62,20 @@ def group_norm_variables(config):
   return [s + "/" + v for s in group_norm_scopes(config) for v in ("gamma", "beta")]
 
 
+def conv_head_variables(config):
+  """Names of the variables a --use_conv_frcnn_head graph needs on top of the output layers, in execution order (reference
+  conv_frcnn_head, models.py:1110-1124): fastrcnn/conv{k}/{W,b}, under use_gn each followed by fastrcnn/gn{k}/{gamma,beta},
+  then fastrcnn/fc/{W,b}.  [] without the flag."""
+  if not getattr(config, "use_conv_frcnn_head", False):
+    return []
+  out = []
+  for k in range(4):
+    out += ["fastrcnn/conv%d/W" % k, "fastrcnn/conv%d/b" % k]
+    if getattr(config, "use_gn", False):
+      out += ["fastrcnn/gn%d/gamma" % k, "fastrcnn/gn%d/beta" % k]
+  return out + ["fastrcnn/fc/W", "fastrcnn/fc/b"]
+
+
 def backbone_conv_specs(config):
   """Yield (scope, kh, cin, cout, has_bn, has_bias) for every conv on the path,
   in execution order (reference nn.py:843-1014, models.py:979-1009); cin is W's third dimension -- the channels per
@@ -156,10 +170,15 @@ def synthetic_weights(config, seed=0):
   dim = config.fpn_frcnn_fc_head_dim
   ch = config.fpn_num_channel
   nc = config.num_class
-  w["fastrcnn/fc6/W"] = normal((ch * 49, dim), np.sqrt(2.0 / (ch * 49)))
-  w["fastrcnn/fc6/b"] = normal((dim,), 0.02)
-  w["fastrcnn/fc7/W"] = normal((dim, dim), np.sqrt(2.0 / dim))
-  w["fastrcnn/fc7/b"] = normal((dim,), 0.02)
+  # --use_conv_frcnn_head: the four fc6 / fc7 draws are made and dropped (every other variable stays bit-identical to the weights
+  # of the same seed without the flag); the head's own variables come from a generator of their own, below
+  conv_head = bool(getattr(config, "use_conv_frcnn_head", False))
+  fcs = {"fastrcnn/fc6/W": normal((ch * 49, dim), np.sqrt(2.0 / (ch * 49)))}
+  fcs["fastrcnn/fc6/b"] = normal((dim,), 0.02)
+  fcs["fastrcnn/fc7/W"] = normal((dim, dim), np.sqrt(2.0 / dim))
+  fcs["fastrcnn/fc7/b"] = normal((dim,), 0.02)
+  if not conv_head:
+    w.update(fcs)
   w["fastrcnn/outputs/class/W"] = normal((dim, nc), 0.05)
   w["fastrcnn/outputs/class/b"] = normal((nc,), 0.02)
   if getattr(config, "add_mask", False):           # maskrcnn_up4conv_head (models.py:1173-1199)
@@ -215,6 +234,21 @@ def synthetic_weights(config, seed=0):
         gamma *= np.float32(0.25)
       w[scope + "/gamma"] = gamma
       w[scope + "/beta"] = g_rng.standard_normal(C, dtype=np.float32) * np.float32(0.02)
+  if conv_head:
+    # --use_conv_frcnn_head (models.py:1110-1124): He-init 3x3 convs, biases N(0, 0.02), fc drawn as fc6 is; under use_gn
+    # fastrcnn/gn{k} with gamma ~ U[0.9, 1.1], beta ~ N(0, 0.02)
+    h_rng = np.random.default_rng([seed, 9])
+    dc = int(getattr(config, "conv_frcnn_head_dim", 256))
+    cin = ch
+    for k in range(4):
+      w["fastrcnn/conv%d/W" % k] = h_rng.standard_normal((3, 3, cin, dc), dtype=np.float32) * np.float32(np.sqrt(2.0 / (9 * cin)))
+      w["fastrcnn/conv%d/b" % k] = h_rng.standard_normal((dc,), dtype=np.float32) * np.float32(0.02)
+      if use_gn:
+        w["fastrcnn/gn%d/gamma" % k] = h_rng.uniform(0.9, 1.1, dc).astype(np.float32)
+        w["fastrcnn/gn%d/beta" % k] = h_rng.standard_normal(dc, dtype=np.float32) * np.float32(0.02)
+      cin = dc
+    w["fastrcnn/fc/W"] = h_rng.standard_normal((dc * 49, dim), dtype=np.float32) * np.float32(np.sqrt(2.0 / (dc * 49)))
+    w["fastrcnn/fc/b"] = h_rng.standard_normal((dim,), dtype=np.float32) * np.float32(0.02)
   return w
 
 

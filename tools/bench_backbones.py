@@ -20,6 +20,12 @@ python tools/bench_backbones.py --backbones r101,r50_gn,r101_gn
   times the GroupNorm launches (csrc/group_norm.hip: statistics, finalize, apply per layer) and prints their share of the step
   next to the byte floor that describe() computes from the plan's own tensors -- every layer reads its conv output twice and
   writes it once, the block tails and the FPN sums read a residual on top -- over the measured copy rate.
+python tools/bench_backbones.py --backbones r101,r101_convhead,r50_gn,r50_gn_convhead,r101_gn,r101_gn_convhead
+  The 4-conv + FC box head (--use_conv_frcnn_head, conv_frcnn_head_dim 256) next to its 2-FC counterparts, in one run:
+  profiles/backbones_convhead_b8_1080p.txt.  A profiled pass times the four head convs (fastrcnn/conv0..3: 3x3 over B x topk RoIs
+  of 7 x 7) against their FLOP at the sustained rate of the fp16x2 kernels, and under --use_gn the four ROI GroupNorms
+  (csrc/group_norm_roi.hip: one launch, one pass each) against the byte floor describe() computes from the plan's own tensors --
+  one read and one write -- over the measured copy rate.
 One JSON line per backbone, and one with all of them at the end."""
 import argparse, json, os, subprocess, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -27,9 +33,12 @@ import numpy as np
 
 COPY_RATE = 6.29e12      # bytes/s, the project's measured device copy rate
 F32_MFMA_RATE = 155e12   # FLOP/s, v_mfma_f32_16x16x4_f32 back to back on every SIMD
+H2_RATE = 341e12         # FLOP/s of f32 work the fp16x2 conv kernels sustain over the R101 step (README.md)
 BACKBONES = {"r101": {}, "resnext101": dict(use_resnext=True), "resnet34": dict(resnet34=True), "resnet18": dict(resnet18=True),
              "r101_nodil": dict(use_dilations=False), "r101_deformable": dict(use_dilations=False, use_deformable=True),
-             "r50_gn": dict(resnet50=True, use_gn=True), "r101_gn": dict(use_gn=True)}
+             "r50_gn": dict(resnet50=True, use_gn=True), "r101_gn": dict(use_gn=True),
+             "r101_convhead": dict(use_conv_frcnn_head=True), "r50_gn_convhead": dict(resnet50=True, use_gn=True, use_conv_frcnn_head=True),
+             "r101_gn_convhead": dict(use_gn=True, use_conv_frcnn_head=True)}
 DEFAULT = ("r101", "resnext101", "resnet34", "resnet18")   # what a run without --backbones measures (profiles/backbones_b8_1080p.txt)
 
 
@@ -129,6 +138,22 @@ def child(a, name):
     per_fwd = dp["group_norm_profiled_ms"] / max(1, dp["profiled_forwards"])
     res["group_norm"] = {"layers": d["group_norms"], "ms_per_step": per_fwd, "share_of_step": per_fwd / res["step_ms"],
                          "bytes_per_step": d["group_norm_floor_bytes"], "floor_ms_bytes_over_copy_rate": d["group_norm_floor_bytes"] / COPY_RATE * 1e3}
+  res["box_head"] = d["box_head"]
+  if d["box_head"] == "4conv1fc":
+    e.profile(True)
+    run(a.steps)
+    dp = e.describe()
+    layers = [(nm, fl, ms) for nm, fl, ms, _ in e.profile_layers() if nm.startswith("fastrcnn/conv")]
+    e.profile(False)
+    n = max(1, dp["profiled_forwards"])
+    assert len(layers) == 4, layers
+    fl = sum(f for _, f, _ in layers)
+    res["head_convs"] = {"layers": [nm for nm, _, _ in layers], "ms_per_step": sum(ms for _, _, ms in layers) / n, "flop_per_step": fl,
+                         "floor_ms_flop_over_fp16x2_rate": fl / H2_RATE * 1e3}
+    if dp["roi_group_norms"] > 0:
+      res["roi_group_norm"] = {"layers": dp["roi_group_norms"], "ms_per_step": dp["roi_group_norm_profiled_ms"] / n,
+                               "bytes_per_step": dp["roi_group_norm_floor_bytes"],
+                               "floor_ms_bytes_over_copy_rate": dp["roi_group_norm_floor_bytes"] / COPY_RATE * 1e3}
   m.close()
   print(json.dumps(res), flush=True)
   return res
@@ -163,7 +188,7 @@ def main():
       sys.exit("%s: child exited with %d" % (name, r.returncode))
     res = json.loads(r.stdout.strip().splitlines()[-1])
     out[name] = res
-    line = "%-11s %s %-12s %8.3f ms/step  %7.1f FPS  (%d conv launches, %d fused tails)" % (
+    line = "%-16s %s %-12s %8.3f ms/step  %7.1f FPS  (%d conv launches, %d fused tails)" % (
         name, res["blocks"], res["block_kind"], res["step_ms"], res["fps"], res["conv_launches"], res["bottleneck_tails_fused"])
     print(line)
     if "group_conv" in res:
@@ -182,6 +207,16 @@ def main():
       print("            GroupNorm: %d layers, %.3f ms/step measured in a profiled pass (%.0f %% of the step);  floor from the plan's tensors: "
             "%.1f GB -> %.3f ms at %.2f TB/s" % (g["layers"], g["ms_per_step"], 100.0 * g["share_of_step"], g["bytes_per_step"] / 1e9,
             g["floor_ms_bytes_over_copy_rate"], COPY_RATE / 1e12))
+    if "head_convs" in res:
+      g = res["head_convs"]
+      print("            4-conv head: %s, %.3f ms/step measured in a profiled pass;  %.2f TFLOP -> %.3f ms at the %.0f TF the fp16x2 "
+            "kernels sustain (measured / floor %.2f)" % (" ".join(n.split("/")[-1] for n in g["layers"]), g["ms_per_step"], g["flop_per_step"] / 1e12,
+            g["floor_ms_flop_over_fp16x2_rate"], H2_RATE / 1e12, g["ms_per_step"] / g["floor_ms_flop_over_fp16x2_rate"]))
+    if "roi_group_norm" in res:
+      g = res["roi_group_norm"]
+      print("            ROI GroupNorm: %d layers, %.3f ms/step measured;  floor from the plan's tensors (one read + one write): %.2f GB -> "
+            "%.3f ms at %.2f TB/s (measured / floor %.2f)" % (g["layers"], g["ms_per_step"], g["bytes_per_step"] / 1e9,
+            g["floor_ms_bytes_over_copy_rate"], COPY_RATE / 1e12, g["ms_per_step"] / g["floor_ms_bytes_over_copy_rate"]))
   print(json.dumps(out), flush=True)
 
 
