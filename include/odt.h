@@ -127,6 +127,12 @@ typedef struct odt_config {
                              * followed by GroupNorm per RoI (fastrcnn/gn{0..3}/{gamma,beta}; csrc/group_norm_roi.hip: one launch, one
                              * pass) with nothing behind it.  Any backbone; with or without add_mask */
   int32_t conv_head_dim;    /* conv_frcnn_head_dim (256): channels of the four head convs; a multiple of 32 in [32, 512] */
+  int32_t add_relation_nn;  /* --add_relation_nn (relation_network, nn.py:115-190; models.py:1044-1054): in the 2-FC box head
+                             * h6' = h6 + RM_r1(h6, boxes) feeds fc7 and h7' = h7 + RM_r2(h7, boxes) feeds the output layers.  A
+                             * module is 16-head self-attention over the image's proposals with a geometric bias on the logits --
+                             * variables fastrcnn/RM_r{1,2}/{geo_emb/{W [4,64], b}, geo_conv/{W [1,1,64,16], b}, query_linear/W,
+                             * key_linear/W [D,D], output_linear/W [16 D, D]} (csrc/relation.hip).  Single-image graph (every image
+                             * of a batch on its own), rpn_topk <= 1024, head_dim a multiple of 64 up to 1024; not with use_conv_frcnn_head */
 } odt_config;
 
 /* conv_arith: all modes keep f32 tensors and f32 accumulation.  ODT_ARITH_F32: every product on the exact-f32 MFMA
@@ -557,6 +563,17 @@ int odt_op_group_norm(int device, const float* x, int B, int Ha, int Wa, int ldc
  * channel C.  amax [1]: the |max| the kernel recorded for out; mean, var [R,32]. */
 int odt_op_group_norm_roi(int device, const float* x, int R, int h, int w, int ldc, int C, const float* gamma, const float* beta,
                           float eps, float* out, float* amax, float* mean, float* var);
+/* The relation module's geometric bias (csrc/relation.hip; --add_relation_nn) as the plan runs it: boxes [K,4] (x1, y1, x2, y2), of which
+ * the first n (0 <= n <= K <= 1024) are real; wts [1360] = geo_emb/W [4,64] | geo_emb/b [64] | geo_conv/W [64,16] | geo_conv/b [16].
+ * bias [16, K, Kp] with Kp = K rounded up to 4: bias[h][i][j] = log(max(relu(a[i,j,h]), 1e-6)) for i, j < n; every other entry comes
+ * back as it went in. */
+int odt_op_relation_geo(int device, const float* boxes, int K, int n, const float* wts, float* bias);
+/* ... and its attention: q, k, v [K, D] (D % 64 == 0, D <= 1024; head h is columns h D/16 ...), bias [16, K, Kp].  out holds out_elems
+ * >= K * 16 * D floats: out[i][h][:] = sum_{j<n} softmax_j(q_h[i] . k_h[j] / sqrt(D / 16) + bias[h][i][j]) v[j][:] for i < n, zeros for
+ * n <= i < K, and what it held past K * 16 * D.  Rows >= n of q, k, v and entries of bias with i >= n or j >= n are never read.
+ * amax [1]: the |max| the kernel recorded for out. */
+int odt_op_relation_attention(int device, const float* q, const float* k, const float* v, const float* bias, int K, int D, int n,
+                              float* out, size_t out_elems, float* amax);
 /* BiFPN node input fusion (launch_bifpn_fuse): n = 1..3 inputs ins[k] [B,in_hw[k][0],in_hw[k][1],ldc], mode[k] 0 same
  * size, 1 nearest resize, 2 3x3 / s2 'SAME' max pool with pads[k] = (top, left); wsm != NULL: 'fastattn' with the raw
  * WSM scalars [n], else a plain sum; act 0 / 2 (swish).  out [B,h,w,ldc]. */

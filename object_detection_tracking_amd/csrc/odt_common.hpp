@@ -506,6 +506,39 @@ struct RoiGroupNormParams {
 };
 int launch_group_norm_roi(const RoiGroupNormParams& p, hipStream_t stream);
 
+// ------------------------------------------------------- relation module of the box head (relation.hip; --add_relation_nn)
+// The two kernels behind RM_r1 / RM_r2 (reference nn.py:115-190, 273-298) over the K proposal rows of each of B images on its
+// own (blockIdx.z), of which the first n = min(count[b], K) are real.  16 heads; plain f32 in every arithmetic mode.
+constexpr int kRelHeads = 16;        // `group` of relation_network
+constexpr int kRelGeoDim = 64;       // geo_feat_dim
+constexpr int kRelMaxK = 1024;       // proposals per image the attention kernel keeps a score row for
+constexpr int kRelMaxD = 1024;       // widest feature vector (a multiple of 64)
+constexpr int kRelGeoWeights = 4 * kRelGeoDim + kRelGeoDim + kRelGeoDim * kRelHeads + kRelHeads;      // 1360
+inline int relation_kp(int K) { return (K + 3) & ~3; }      // row pitch of the bias tensor: 16-byte rows
+// geometric bias: boxes [K,4] (x1, y1, x2, y2) -> bias [16, K, Kp], bias[h][i][j] = log(max(relu(a[i,j,h]), 1e-6)).  Entries with
+// i >= n or j >= n are neither evaluated nor written
+struct RelationGeoParams {
+  const float* boxes;    // [B,K,4]
+  const int* count;      // [B]: the images' proposal counts
+  const float* wts;      // [1360]: geo_emb/W [4,64] | geo_emb/b [64] | geo_conv/W [64,16] | geo_conv/b [16]
+  float* bias;           // [B, 16, K, Kp]
+  int B, K, Kp;
+};
+int launch_relation_geo(const RelationGeoParams& p, hipStream_t stream);
+// attention: S[i,h,j] = (Q_h[i] . K_h[j]) / sqrt(D / 16) + bias[h][i][j], P = softmax over j < n, O[i,h,:] = sum_j P[i,h,j] v[j,:].
+// Rows i >= n of O are written as zeros; columns j >= n and rows >= n of q, k, v and bias are never read
+struct RelationAttnParams {
+  const float* q;        // [B K, D] at pitch qk_ldc; head h is columns h D/16 .. (h+1) D/16
+  const float* k;        // [B K, D] at pitch qk_ldc
+  const float* v;        // [B K, D] at pitch v_ldc: the module's input
+  const float* bias;     // [B, 16, K, Kp]
+  const int* count;      // [B]
+  float* out;            // [B K, 16, D]
+  unsigned* amax;        // range slot of out or nullptr
+  int B, K, Kp, D, qk_ldc, v_ldc;
+};
+int launch_relation_attention(const RelationAttnParams& p, hipStream_t stream);
+
 // ------------------------------------------------------- EfficientDet tail (effdet_post.hip)
 struct EffPostParams {
   const float* cls[5];     // per level [B, npix, ldc_cls]  (9 * ncls valid channels: anchor-major)

@@ -60,7 +60,8 @@ struct ConvOp {
 
 enum OpKind { OP_PRE, OP_CONV, OP_POOL, OP_SUB2, OP_PROPOSALS, OP_ROI_HEAD, OP_DETECT, OP_ROI_FINAL,
               OP_ROI_MASK, OP_MASK_SELECT, OP_PRE_RGB, OP_DW, OP_CMEAN, OP_CSCALE, OP_FUSE, OP_EFF_POST, OP_ROI_EFF, OP_SE_GATE,
-              OP_SE_GATE_MEAN, OP_WSCALE, OP_MB_EXPAND_DW, OP_RSE_GATE, OP_RSE_APPLY, OP_GCONV, OP_BLOCK, OP_DCONV, OP_GN, OP_GN_ROI };
+              OP_SE_GATE_MEAN, OP_WSCALE, OP_MB_EXPAND_DW, OP_RSE_GATE, OP_RSE_APPLY, OP_GCONV, OP_BLOCK, OP_DCONV, OP_GN, OP_GN_ROI,
+              OP_RELATION_GEO, OP_RELATION_ATTN };
 struct Op {
   OpKind kind;
   int conv = -1;        // index into convs (OP_BLOCK: the block's conv2, whose record launches conv_block_kernel)
@@ -68,6 +69,7 @@ struct Op {
   int dconv = -1;       // OP_DCONV: its index among the plan's deformable convs (profiling events)
   int gnorm = -1;       // OP_GN: its index among the plan's GroupNorm layers (profiling events)
   int gnroi = -1;       // OP_GN_ROI: its index among the plan's ROI GroupNorm layers (profiling events)
+  int rel = -1;         // OP_RELATION_GEO / OP_RELATION_ATTN: the relation module it belongs to (0: RM_r1, 1: RM_r2; profiling events)
   Tensor in, out;
   DwConvParams dw{};    // OP_DW
   MbExpandDwParams mb{};   // OP_MB_EXPAND_DW
@@ -79,6 +81,8 @@ struct Op {
   DeformConvParams dc{};   // OP_DCONV: a deformable stage entry's conv2_offset + deformable conv2 (conv_deform.hip)
   GroupNormParams gn{};    // OP_GN: GroupNorm of a conv's output + what that conv's epilogue would have carried (group_norm.hip)
   RoiGroupNormParams gnr{};   // OP_GN_ROI: GroupNorm behind a conv of the 4-conv box head, per ROI (group_norm_roi.hip)
+  RelationGeoParams rg{};     // OP_RELATION_GEO: the geometric bias of a relation module (relation.hip)
+  RelationAttnParams ra{};    // OP_RELATION_ATTN: its attention, softmax(Q K^T / sqrt(dh) + bias) V per head (relation.hip)
   float* aux = nullptr; // OP_CMEAN: means out [B,ldc]; OP_CSCALE / OP_WSCALE: gates in [B,ldc]
   const float* wt0 = nullptr;   // OP_WSCALE: the conv's unscaled weights [Cout][K] (conv = index of the conv whose weights are rebuilt)
   float* aux2 = nullptr;   // OP_CMEAN: partial-sum scratch
@@ -140,6 +144,7 @@ struct odt_model {
   int dconv_ops = 0;                 // odt_config.use_deformable: stage entries that run conv2_offset + the deformable conv2 (conv_deform.hip)
   int gn_ops = 0;                    // odt_config.use_gn: GroupNorm layers, three launches each (group_norm.hip)
   int gn_roi_ops = 0;                // odt_config.use_gn + use_conv_frcnn_head: ROI GroupNorm layers of the box head, one launch each (group_norm_roi.hip)
+  int rel_modules = 0;               // odt_config.add_relation_nn: relation modules of the box head (RM_r1, RM_r2), two launches each (relation.hip)
   int mb_fused = 0;                  // EfficientNet: MBConv blocks whose expand + depthwise run as one kernel (effnet_mbconv.hip)
   // tail overlap: the selection / ROIAlign / box-head / NMS kernels of forward i (a few dozen workgroups each,
   // ~2 ms per 8-frame step) run on a side stream under the backbone of forward i+1.  The next forward's FPN stage
@@ -192,6 +197,8 @@ struct odt_model {
   double prof_gn_ms = 0;
   std::vector<hipEvent_t> ev_gn_roi; // OP_GN_ROI i: events [2 i, 2 i + 1]
   double prof_gn_roi_ms = 0;
+  std::vector<hipEvent_t> ev_rel;    // relation module i: events [4 i, 4 i + 3] (geo before / after, attention before / after)
+  double prof_rel_geo_ms[2] = {0, 0}, prof_rel_attn_ms[2] = {0, 0};
   int prof_forwards = 0;
   int prof_launches = 0;
 
@@ -323,6 +330,8 @@ void visit_op_ptrs(odt_model* m, size_t oi, F&& f) {
     // (part / ab / mean / var are dedicated allocations shared by the plan's GroupNorm layers: attach_group_norm_scratch)
     case OP_GN: f(op.gn.x); f(op.gn.res); f(op.gn.out); break;
     case OP_GN_ROI: f(op.gnr.x); f(op.gnr.out); break;      // (mean / var, where kept, are dedicated allocations)
+    case OP_RELATION_GEO: f(op.rg.boxes); f(op.rg.bias); break;
+    case OP_RELATION_ATTN: f(op.ra.q); f(op.ra.k); f(op.ra.v); f(op.ra.bias); f(op.ra.out); break;
     case OP_FUSE: for (auto& p : op.fuse.in) f(p); f(op.fuse.out); break;
     case OP_EFF_POST: for (auto& p : m->eff_post.cls) f(p); for (auto& p : m->eff_post.box) f(p); break;
     case OP_CMEAN: case OP_CSCALE: case OP_SE_GATE: case OP_SE_GATE_MEAN: case OP_WSCALE: case OP_POOL: case OP_SUB2: break;

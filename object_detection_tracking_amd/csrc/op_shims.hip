@@ -1143,6 +1143,54 @@ int odt_op_group_norm_roi(int device, const float* x, int R, int h, int w, int l
   return get_dev(out, dout, n);
 }
 
+int odt_op_relation_geo(int device, const float* boxes, int K, int n, const float* wts, float* bias) {
+  ODT_CHECK(boxes && wts && bias, "odt_op_relation_geo: null argument");
+  ODT_CHECK(K >= 1, "odt_op_relation_geo: bad sizes");
+  ODT_CHECK(K <= kRelMaxK, "odt_op_relation_geo: at most " + std::to_string(kRelMaxK) + " proposals (K = " + std::to_string(K) + ")");
+  ODT_CHECK(n >= 0 && n <= K, "odt_op_relation_geo: the proposal count n = " + std::to_string(n) + " is not in [0, K = " + std::to_string(K) + "]");
+  if (set_dev(device)) return 1;
+  GBufs g;
+  RelationGeoParams p; std::memset(&p, 0, sizeof(p));
+  const int Kp = relation_kp(K);
+  const size_t nb = (size_t)kRelHeads * K * Kp;
+  float *db, *dw, *dbias;
+  int* dn;
+  // (bias starts as a copy of the caller's buffer: what the kernel does not evaluate must come back as it went in)
+  if (g.alloc("boxes", (size_t)K * 4, &db, -1, boxes) || g.alloc("weights", (size_t)kRelGeoWeights, &dw, -1, wts) ||
+      g.alloc("count", (size_t)1, &dn, -1, &n) || g.alloc("bias", nb, &dbias, -1, bias)) return 1;
+  p.boxes = db; p.count = dn; p.wts = dw; p.bias = dbias; p.B = 1; p.K = K; p.Kp = Kp;
+  if (launch_relation_geo(p, nullptr)) return 1;
+  if (g.check("odt_op_relation_geo")) return 1;
+  return get_dev(bias, dbias, nb);
+}
+
+int odt_op_relation_attention(int device, const float* q, const float* k, const float* v, const float* bias, int K, int D, int n,
+                              float* out, size_t out_elems, float* amax) {
+  ODT_CHECK(q && k && v && bias && out && amax, "odt_op_relation_attention: null argument");
+  ODT_CHECK(K >= 1 && D >= 1, "odt_op_relation_attention: bad sizes");
+  ODT_CHECK(K <= kRelMaxK, "odt_op_relation_attention: at most " + std::to_string(kRelMaxK) + " proposals (K = " + std::to_string(K) + ")");
+  ODT_CHECK(D % 64 == 0 && D <= kRelMaxD,
+            "odt_op_relation_attention: D must be a multiple of 64 in [64, " + std::to_string(kRelMaxD) + "] (D = " + std::to_string(D) + ")");
+  ODT_CHECK(n >= 0 && n <= K, "odt_op_relation_attention: the proposal count n = " + std::to_string(n) + " is not in [0, K = " + std::to_string(K) + "]");
+  ODT_CHECK(out_elems >= (size_t)K * kRelHeads * D, "odt_op_relation_attention: out is smaller than [K,16,D]");
+  if (set_dev(device)) return 1;
+  GBufs g;
+  RelationAttnParams p; std::memset(&p, 0, sizeof(p));
+  const int Kp = relation_kp(K);
+  float *dq, *dk, *dv, *dbias, *dout;
+  int* dn;
+  unsigned* slot;
+  if (g.alloc("q", (size_t)K * D, &dq, -1, q) || g.alloc("k", (size_t)K * D, &dk, -1, k) || g.alloc("v", (size_t)K * D, &dv, -1, v) ||
+      g.alloc("bias", (size_t)kRelHeads * K * Kp, &dbias, -1, bias) || g.alloc("count", (size_t)1, &dn, -1, &n) ||
+      g.alloc("out", out_elems, &dout, -1, out) || g.alloc("range slot", (size_t)kAmaxWays, &slot, 0)) return 1;
+  p.q = dq; p.k = dk; p.v = dv; p.bias = dbias; p.count = dn; p.out = dout; p.amax = slot;
+  p.B = 1; p.K = K; p.Kp = Kp; p.D = D; p.qk_ldc = D; p.v_ldc = D;
+  if (launch_relation_attention(p, nullptr)) return 1;
+  if (g.check("odt_op_relation_attention")) return 1;
+  if (rse_read_amax(slot, amax)) return 1;
+  return get_dev(out, dout, out_elems);
+}
+
 int odt_op_effdet_post(int device, int B, int ncls, const int32_t* npix, int ldc_cls, int ldc_box,
                        const float* const* cls, const float* const* box, const float* anchors, int k, int max_out,
                        float score_thresh, float iou_thresh, float image_scale, int32_t* cand_idx, float* cand_boxes,

@@ -402,6 +402,18 @@ int attach_split_weights(odt_model* m) {
       if (m->range_slot_name[slot].empty()) m->range_slot_name[slot] = "ROI GroupNorm output";
       continue;
     }
+    if (op.kind == OP_RELATION_ATTN) {
+      // a relation module's attention output, likewise: output_linear (K = 16 D) reads it
+      slot_of.erase(op.ra.out);
+      if (pol.family != 2) continue;
+      const int g = tail ? 1 : 0;
+      ODT_CHECK(m->amax_used[g] < odt_model::kAmaxSlots, "too many conv outputs for the range slots");
+      const int slot = (tail ? odt_model::kAmaxSlots : 0) + m->amax_used[g]++;
+      slot_of[op.ra.out] = slot;
+      m->ops[oi].ra.amax = m->amax_dev + (size_t)slot * kAmaxWays;
+      m->range_slot_name[slot] = op.rel == 0 ? "rm_r1_attn" : "rm_r2_attn";
+      continue;
+    }
     if (op.kind == OP_POOL || op.kind == OP_SUB2) {
       auto it = slot_of.find(op.in.d);
       if (it != slot_of.end()) slot_of[op.out.d] = it->second; else slot_of.erase(op.out.d);

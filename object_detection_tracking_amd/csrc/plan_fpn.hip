@@ -126,6 +126,65 @@ int concat_cout(odt_model* m, const std::string& a, int na, const std::string& b
   return 0;
 }
 
+// One relation module of the box head (--add_relation_nn; relation_network nn.py:115-190 from models.py:1044-1054): out = f +
+// RM(f, boxes) over the proposals of each image, f [1,1,B K,D].  Four launches: Q | K = f [query_linear/W | key_linear/W] as ONE
+// 1x1 conv (no bias), the geometric bias and the attention (relation.hip), and output_linear over the [B K, 16 D] attention output
+// as a 1x1 conv whose epilogue adds f -- a residual with no activation behind it, as the FPN's top-down sum has.  `geo` is the
+// [B,16,K,Kp] bias buffer, shared by the two modules.  Stage names: `tap` (the sum) and `tap`_attn (the attention output)
+int relation_module(odt_model* m, int index, const std::string& scope, const Tensor& f, const Tensor& props, const Tensor& geo,
+                    const std::string& tap, Tensor* out) {
+  const odt_config& cfg = m->cfg;
+  const int B = cfg.batch, K = cfg.rpn_topk, D = cfg.head_dim, R = B * K;
+  struct Var { const char* name; size_t elems; const char* shape; };
+  const Var vars[7] = {{"geo_emb/W", (size_t)4 * kRelGeoDim, "[4,64]"}, {"geo_emb/b", (size_t)kRelGeoDim, "[64]"},
+                       {"geo_conv/W", (size_t)kRelGeoDim * kRelHeads, "[1,1,64,16]"}, {"geo_conv/b", (size_t)kRelHeads, "[16]"},
+                       {"query_linear/W", (size_t)D * D, "[D,D]"}, {"key_linear/W", (size_t)D * D, "[D,D]"},
+                       {"output_linear/W", (size_t)kRelHeads * D * D, "[16 D,D]"}};
+  const HostTensor* w[7];
+  for (int i = 0; i < 7; ++i) {
+    w[i] = find_w(m, scope + "/" + vars[i].name);
+    ODT_CHECK(w[i] != nullptr, "missing relation variable " + scope + "/" + vars[i].name + " (odt_config.add_relation_nn)");
+    ODT_CHECK(w[i]->data.size() == vars[i].elems, "bad shape for " + scope + "/" + vars[i].name + " (" + vars[i].shape + " with D = " +
+                                                      std::to_string(D) + ")");
+  }
+  {   // [query_linear/W | key_linear/W] side by side along Cout
+    HostTensor v; v.data.resize((size_t)D * 2 * D);
+    for (int i = 0; i < D; ++i) {
+      std::memcpy(&v.data[(size_t)i * 2 * D], &w[4]->data[(size_t)i * D], sizeof(float) * D);
+      std::memcpy(&v.data[(size_t)i * 2 * D + D], &w[5]->data[(size_t)i * D], sizeof(float) * D);
+    }
+    m->host_w["__" + tap + "qk/W"] = v;
+  }
+  Tensor qk{};
+  ConvSpec cq(scope + "/query_key_linear", f, D, 2 * D);
+  if (upload_conv_plain(m, "__" + tap + "qk", 1, 1, D, 2 * D, false, &cq.wt, &cq.bias) || add_conv(m, cq, &qk)) return 1;
+  m->host_w.erase("__" + tap + "qk/W");
+  Op og; og.kind = OP_RELATION_GEO; og.rel = index;
+  {
+    std::vector<float> gw;
+    for (int i = 0; i < 4; ++i) gw.insert(gw.end(), w[i]->data.begin(), w[i]->data.end());
+    RelationGeoParams& g = og.rg;
+    std::memset(&g, 0, sizeof(g));
+    if (upload_raw(m, gw, &g.wts)) return 1;
+    g.boxes = props.d; g.count = m->prop.nprops; g.bias = geo.d; g.B = B; g.K = K; g.Kp = geo.C;
+  }
+  m->ops.push_back(og);
+  Tensor att{};
+  if (make_tensor(m, tap + "_attn", 1, 1, R, kRelHeads * D, &att)) return 1;
+  Op oa; oa.kind = OP_RELATION_ATTN; oa.rel = index; oa.out = att;
+  {
+    RelationAttnParams& a = oa.ra;
+    std::memset(&a, 0, sizeof(a));
+    a.q = qk.d; a.k = qk.d + D; a.qk_ldc = qk.C; a.v = f.d; a.v_ldc = f.C; a.bias = geo.d; a.count = m->prop.nprops; a.out = att.d;
+    a.B = B; a.K = K; a.Kp = geo.C; a.D = D;
+  }
+  m->ops.push_back(oa);
+  ++m->rel_modules;
+  ConvSpec co(scope + "/output_linear", att, kRelHeads * D, D);
+  co.res = &f; co.res_mode = 1; co.tap = tap;
+  return upload_conv_plain(m, scope + "/output_linear", 1, 1, kRelHeads * D, D, false, &co.wt, &co.bias) || add_conv(m, co, out);
+}
+
 // ---- front end (nn.py:860-896; tf_pad_reverse => pad [3, 2 + pad_to_32]): image pad, conv0, pool0 -> the pooled map
 int front_end(odt_model* m, Tensor* pool) {
   const int B = m->cfg.batch, H = m->cfg.height, W = m->cfg.width;
@@ -491,6 +550,7 @@ int box_head(odt_model* m, const Tensor P[5], const Tensor& props, Tensor* hout)
     // BEHIND the ReLU and with no activation of its own -- then ONE dense layer fastrcnn/fc + ReLU; no fc6 / fc7.  Rows past
     // nprops[b] are zero RoIs: finite through every layer, normalised like any other row
     const int DC = cfg.conv_head_dim, R = B * K;
+    ODT_CHECK(cfg.add_relation_nn == 0, "add_relation_nn: not built with use_conv_frcnn_head (the reference ignores the flag there)");
     ODT_CHECK(DC >= 32 && DC <= 512 && DC % 32 == 0, "use_conv_frcnn_head: odt_config.conv_head_dim must be a multiple of 32 in [32, 512]");
     Tensor cur = roi;
     cur.B = R; cur.H = cur.h = kRoiOut; cur.W = cur.w = kRoiOut; cur.C = cur.c = FC;
@@ -518,13 +578,27 @@ int box_head(odt_model* m, const Tensor P[5], const Tensor& props, Tensor* hout)
     cf.relu = 1; cf.tap = "head_fc";
     if (upload_conv(m, "__headfc", 1, 1, 49 * DC, D, false, &cf.wt, &cf.bias) || add_conv(m, cf, &h7)) return 1;
   } else {
+    // --add_relation_nn (models.py:1044-1054): h6' = h6 + RM_r1(h6, boxes) feeds fc7, h7' = h7 + RM_r2(h7, boxes) the output layers
+    const bool rel = cfg.add_relation_nn != 0;
+    Tensor geo{};
+    if (rel) {
+      ODT_CHECK(cfg.graph == ODT_GRAPH_SINGLE, "add_relation_nn: built for the single-image graph only (the batched graph of the reference "
+                                               "calls the head without boxes)");
+      ODT_CHECK(K <= kRelMaxK, "add_relation_nn: rpn_topk = " + std::to_string(K) + " proposals per image, at most " + std::to_string(kRelMaxK));
+      ODT_CHECK(D % 64 == 0 && D <= kRelMaxD, "add_relation_nn: head_dim = " + std::to_string(D) + ", not a multiple of 64 up to " +
+                                                  std::to_string(kRelMaxD));
+      if (make_tensor(m, "", B, kRelHeads, K, relation_kp(K), &geo)) return 1;
+    }
     if (flat_dense("fastrcnn/fc6", FC, "__fc6")) return 1;
     ConvSpec c6("fastrcnn/fc6", roi, 49 * FC, D);
     c6.relu = 1; c6.tap = "fc6";
     if (upload_conv(m, "__fc6", 1, 1, 49 * FC, D, false, &c6.wt, &c6.bias) || add_conv(m, c6, &h6)) return 1;
+    Tensor h6r{}, h7r{};
+    if (rel) { if (relation_module(m, 0, "fastrcnn/RM_r1", h6, props, geo, "rm_r1", &h6r)) return 1; h6 = h6r; }
     ConvSpec c7("fastrcnn/fc7", h6, D, D);
     c7.relu = 1; c7.tap = "fc7";
     if (conv_layer(m, c7, false, &h7)) return 1;
+    if (rel) { if (relation_module(m, 1, "fastrcnn/RM_r2", h7, props, geo, "rm_r2", &h7r)) return 1; h7 = h7r; }
   }
   if (concat_cout(m, "fastrcnn/outputs/class", C, "fastrcnn/outputs/box", 4 * C, D, "__headout")) return 1;
   ConvSpec co("fastrcnn/outputs", h7, D, C * 5);

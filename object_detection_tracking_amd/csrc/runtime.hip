@@ -153,6 +153,16 @@ static int run_ops(odt_model* m, const void* src, int dtype, hipStream_t st, siz
         if (launch_group_norm_roi(op.gnr, st)) return 1;
         if (m->profile) ODT_HIP(hipEventRecord(m->ev_gn_roi[2 * op.gnroi + 1], st));
         break;
+      case OP_RELATION_GEO:       // --add_relation_nn: the geometric bias of a relation module of the box head
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_rel[4 * op.rel], st));
+        if (launch_relation_geo(op.rg, st)) return 1;
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_rel[4 * op.rel + 1], st));
+        break;
+      case OP_RELATION_ATTN:      // ... and its attention
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_rel[4 * op.rel + 2], st));
+        if (launch_relation_attention(op.ra, st)) return 1;
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_rel[4 * op.rel + 3], st));
+        break;
       case OP_MASK_SELECT:
         if (launch_mask_select(m->mask_sel, st)) return 1;
         break;
@@ -239,6 +249,12 @@ static int finish_profile(odt_model* m, hipStream_t st) {
     ODT_HIP(hipEventElapsedTime(&t, m->ev_gn_roi[2 * i], m->ev_gn_roi[2 * i + 1]));
     m->prof_gn_roi_ms += t;
   }
+  for (int i = 0; i < m->rel_modules && i < 2; ++i) {
+    float t0 = 0, t1 = 0;
+    ODT_HIP(hipEventElapsedTime(&t0, m->ev_rel[4 * i], m->ev_rel[4 * i + 1]));
+    ODT_HIP(hipEventElapsedTime(&t1, m->ev_rel[4 * i + 2], m->ev_rel[4 * i + 3]));
+    m->prof_rel_geo_ms[i] += t0; m->prof_rel_attn_ms[i] += t1;
+  }
   ++m->prof_forwards;
   float tt = 0;
   ODT_HIP(hipEventElapsedTime(&tt, m->ev_total[0], m->ev_total[1]));
@@ -288,6 +304,7 @@ int run_plan(odt_model* m, const void* frames, int dtype, int on_device, hipStre
     while (m->ev_dconv.size() < 3 * (size_t)m->dconv_ops) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_dconv.push_back(e); }
     while (m->ev_gn.size() < 2 * (size_t)m->gn_ops) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_gn.push_back(e); }
     while (m->ev_gn_roi.size() < 2 * (size_t)m->gn_roi_ops) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_gn_roi.push_back(e); }
+    while (m->ev_rel.size() < 4 * (size_t)m->rel_modules) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_rel.push_back(e); }
     for (int i = 0; i < 2; ++i) if (!m->ev_total[i]) ODT_HIP(hipEventCreate(&m->ev_total[i]));
     ODT_HIP(hipEventRecord(m->ev_total[0], st));
   }
@@ -378,6 +395,7 @@ int odt_destroy(odt_handle h) {
   for (auto e : h->ev_dconv) (void)hipEventDestroy(e);
   for (auto e : h->ev_gn) (void)hipEventDestroy(e);
   for (auto e : h->ev_gn_roi) (void)hipEventDestroy(e);
+  for (auto e : h->ev_rel) (void)hipEventDestroy(e);
   for (auto e : h->ev_total) if (e) (void)hipEventDestroy(e);
   for (auto& sl : h->slot) {
     if (sl.pin_in) (void)hipHostFree(sl.pin_in);
@@ -733,6 +751,7 @@ int odt_profile_enable(odt_handle h, int enable) {
   h->prof_doff_ms = h->prof_dconv_ms = 0;
   h->prof_gn_ms = 0;
   h->prof_gn_roi_ms = 0;
+  for (int i = 0; i < 2; ++i) h->prof_rel_geo_ms[i] = h->prof_rel_attn_ms[i] = 0;
   h->prof_layer_ms.assign(h->convs.size(), 0.0);
   return 0;
 }
@@ -815,7 +834,8 @@ int odt_describe(odt_handle h, char* buf, int cap) {
                 "\"group_conv_profiled_ms\": %.6f, \"profiled_forwards\": %d, \"use_deformable\": %d, \"deform_conv_launches\": %d, "
                 "\"deform_offset_profiled_ms\": %.6f, \"deform_conv_profiled_ms\": %.6f, \"use_gn\": %d, \"group_norms\": %d, "
                 "\"group_norm_profiled_ms\": %.6f, \"group_norm_floor_bytes\": %.0f, \"box_head\": \"%s\", \"roi_group_norms\": %d, "
-                "\"roi_group_norm_profiled_ms\": %.6f, \"roi_group_norm_floor_bytes\": %.0f}",
+                "\"roi_group_norm_profiled_ms\": %.6f, \"roi_group_norm_floor_bytes\": %.0f, \"relation_modules\": %d, "
+                "\"relation_geo_profiled_ms\": [%.6f, %.6f], \"relation_attention_profiled_ms\": [%.6f, %.6f]}",
                 h->policy.arith != 0 && fam[2] > 0 ? "f32 through fp16x2 / bf16x3 split products"
                     : (h->policy.arith != 0 && fam[1] + fam[3] > 0 ? "f32 through bf16x3 split products" : "exact f32 MFMA"),
                 (int)h->convs.size() - nfused, nfused, fam[0], fam[1] + fam[3], fam[2], h->convs_h2f, h->blocks_fused, h->stem_fused, h->mb_fused, fam[3], fam[1], fam[2], nsk, h->policy.family,
@@ -825,7 +845,9 @@ int odt_describe(odt_handle h, char* buf, int cap) {
                 h->cfg.block_kind == 1 ? "basic" : (h->cfg.block_kind == 2 ? "resnext32x4d" : "bottleneck"), h->gconv_ops,
                 h->prof_gconv_ms, h->prof_forwards, h->cfg.use_deformable != 0 ? 1 : 0, h->dconv_ops, h->prof_doff_ms, h->prof_dconv_ms,
                 h->cfg.use_gn != 0 ? 1 : 0, h->gn_ops, h->prof_gn_ms, gn_bytes,
-                h->cfg.graph != ODT_GRAPH_EFFNET && h->cfg.use_conv_frcnn_head != 0 ? "4conv1fc" : "2fc", h->gn_roi_ops, h->prof_gn_roi_ms, gn_roi_bytes);
+                h->cfg.graph != ODT_GRAPH_EFFNET && h->cfg.use_conv_frcnn_head != 0 ? "4conv1fc" : (h->rel_modules > 0 ? "2fc+relation" : "2fc"),
+                h->gn_roi_ops, h->prof_gn_roi_ms, gn_roi_bytes, h->rel_modules, h->prof_rel_geo_ms[0], h->prof_rel_geo_ms[1],
+                h->prof_rel_attn_ms[0], h->prof_rel_attn_ms[1]);
   ODT_CHECK((int)std::strlen(tmp) < cap, "odt_describe: buffer too small");
   std::strncpy(buf, tmp, cap - 1); buf[cap - 1] = 0;
   return 0;

@@ -34,7 +34,7 @@ from .range_guard import RangeGuard
 from .frozen_pb import load_frozen_pb
 from .tf_checkpoint import load_checkpoint
 from .weights import (backbone_block_kind, conv_head_variables, deformable_groups, expand_class_agnostic_box, group_norm_variables, load_npz,
-                      select_partial_classes)
+                      relation_variables, select_partial_classes)
 
 
 class TensorHandle(object):
@@ -138,6 +138,7 @@ class _Engine(object):
     c.use_gn = int(bool(getattr(config, "use_gn", False)))      # GroupNorm in the backbone and the FPN
     c.use_conv_frcnn_head = int(bool(getattr(config, "use_conv_frcnn_head", False)))      # 4 convs + one FC in place of fc6 / fc7
     c.conv_head_dim = int(getattr(config, "conv_frcnn_head_dim", 256))
+    c.add_relation_nn = int(bool(getattr(config, "add_relation_nn", False)))      # RM_r1 / RM_r2 behind fc6 / fc7
     B, P, Cn = batch, self.per_im, self.channels
     self._boxes = np.zeros((B, P, 4), np.float32)
     self._probs = np.zeros((B, P), np.float32)
@@ -393,8 +394,7 @@ class _DetectorBase(object):
         raise ValueError("weights: pass a {name: array} dict or set config.model_path to a "
                          "Tensorpack-style .npz (reference obj_detect_tracking.py:417-435), a "
                          "TF checkpoint directory / prefix, or a frozen .pb (--is_load_from_pb)")
-    unsupported = [f for f in ("add_relation_nn", "use_att_frcnn_head",
-                               "use_small_object_head", "use_cascade_rcnn")
+    unsupported = [f for f in ("use_att_frcnn_head", "use_small_object_head", "use_cascade_rcnn")
                    if getattr(self.config, f, False)]
     if unsupported:
       raise NotImplementedError("graph variants not built on this path (SURVEY.md 8, out of scope): "
@@ -408,6 +408,27 @@ class _DetectorBase(object):
       if missing:
         raise NotImplementedError("a GroupNorm graph cannot be built from weights without gn/{gamma,beta} variables: missing "
                                   + ", ".join(missing[:4]) + (" ... (%d in all)" % len(missing) if len(missing) > 4 else ""))
+    if getattr(self.config, "add_relation_nn", False):
+      # --add_relation_nn (nn.py:115-190 from models.py:1044-1054): RM_r1 behind fc6 and RM_r2 behind fc7 of the 2-FC box head;
+      # independent of the backbone, the output layers and the mask head
+      if getattr(self.config, "use_conv_frcnn_head", False):
+        raise NotImplementedError("graph variants not built on this path: add_relation_nn together with use_conv_frcnn_head (the "
+                                  "reference takes the flag for that head, ignores it and says nothing)")
+      if self.graph != ODT_GRAPH_SINGLE:
+        raise NotImplementedError("add_relation_nn is built for the single-image graph (Mask_RCNN_FPN): the reference's batched "
+                                  "graph calls the box head without boxes and cannot build it")
+      topk = int(self.config.rpn_test_post_nms_topk)
+      if topk > 1024:
+        raise NotImplementedError("graph variants not built on this path: add_relation_nn with rpn_test_post_nms_topk = %d (at most "
+                                  "1024: the attention kernel keeps one score row per query in LDS)" % topk)
+      dim = int(self.config.fpn_frcnn_fc_head_dim)
+      if dim < 64 or dim > 1024 or dim % 64 != 0:
+        raise NotImplementedError("graph variants not built on this path: add_relation_nn with fpn_frcnn_fc_head_dim = %d (a "
+                                  "multiple of 64 in [64, 1024]: 16 heads of whole MFMA k-steps, 64-column output chunks)" % dim)
+      missing = [n for n in relation_variables(self.config) if n not in weights]
+      if missing:
+        raise NotImplementedError("a relation-network box head (add_relation_nn) cannot be built from weights without its variables: "
+                                  "missing " + ", ".join(missing[:4]) + (" ... (%d in all)" % len(missing) if len(missing) > 4 else ""))
     if getattr(self.config, "use_conv_frcnn_head", False):
       # --use_conv_frcnn_head (models.py:1110-1124): fastrcnn/conv0..3 (+ fastrcnn/gn0..3 under use_gn) and fastrcnn/fc in place
       # of fc6 / fc7; independent of the backbone, the output layers and the mask head
@@ -679,7 +700,7 @@ def config_from_weights(weights, add_mask=False, is_multi=False, **overrides):
   use_dilations=False follows from it: the only published SE model (version 6) is undilated.  A
   ``groupG/block0/conv2_offset/W`` means deformable stage entries (use_deformable, and no dilations); ``conv0/gn/gamma`` means
   GroupNorm in the backbone and the FPN (use_gn); ``fastrcnn/conv0/W`` means the 4-conv + FC box head (use_conv_frcnn_head, its
-  last axis conv_frcnn_head_dim).  No ``group0/block0/conv3/W``
+  last axis conv_frcnn_head_dim); ``fastrcnn/RM_r1/query_linear/W`` means relation modules in the 2-FC head (add_relation_nn).  No ``group0/block0/conv3/W``
   means basic blocks (use_basic_block); a ``conv2/W`` of [3,3,C/32,C] means ResNeXt-32x4d (use_resnext)."""
   from .config import make_config
   blocks = [0, 0, 0, 0]
@@ -701,6 +722,8 @@ def config_from_weights(weights, add_mask=False, is_multi=False, **overrides):
     kw.update(use_gn=True)                     # GroupNorm variables in place of conv0/bn
   if "fastrcnn/conv0/W" in weights:            # the 4-conv + FC box head; its width is the conv's Cout
     kw.update(use_conv_frcnn_head=True, conv_frcnn_head_dim=int(np.asarray(weights["fastrcnn/conv0/W"]).shape[-1]))
+  if "fastrcnn/RM_r1/query_linear/W" in weights:      # relation modules behind fc6 / fc7
+    kw.update(add_relation_nn=True)
   if "group0/block0/conv3/W" not in weights:
     kw.update(use_basic_block=True)            # resnet_basicblock: two 3x3 convs, no conv3
   else:

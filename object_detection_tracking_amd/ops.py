@@ -610,6 +610,42 @@ def group_norm_roi(x, gamma, beta, eps=1e-5, view=None, out_init=None, lib=None,
   return out, float(amax[0]), mean, var
 
 
+def relation_geo(boxes, n, geo_emb, geo_conv, bias_init=None, lib=None, device=0):
+  """The geometric bias of a relation module as the box head runs it under --add_relation_nn (csrc/relation.hip; reference
+  nn.py:115-143, 273-298): boxes [K,4] (x1, y1, x2, y2), of which the first n are real; geo_emb = (W [4,64], b [64]), geo_conv =
+  (W [1,1,64,16] or [64,16], b [16]).  Returns bias [16, K, Kp] with Kp = K rounded up to 4: bias[h, i, j] =
+  log(max(relu(a[i, j, h]), 1e-6)) for i, j < n; every other entry keeps what bias_init holds (default zeros)."""
+  lib = _L(lib)
+  boxes = f32(boxes)
+  K = boxes.shape[0]
+  assert boxes.shape == (K, 4)
+  wts = np.concatenate([f32(geo_emb[0]).reshape(-1), f32(geo_emb[1]).reshape(-1), f32(geo_conv[0]).reshape(-1),
+                        f32(geo_conv[1]).reshape(-1)])
+  assert wts.size == 1360, wts.size
+  Kp = (K + 3) // 4 * 4
+  bias = np.zeros((16, K, Kp), np.float32) if bias_init is None else f32(bias_init).copy()
+  assert bias.shape == (16, K, Kp)
+  lib.check(lib.dll.odt_op_relation_geo(device, fptr(boxes), K, int(n), fptr(wts), fptr(bias)))
+  return bias
+
+
+def relation_attention(q, k, v, bias, n, out_init=None, lib=None, device=0):
+  """The attention of a relation module (csrc/relation.hip; reference nn.py:146-183): q, k, v [K, D] with 16 heads of D / 16
+  columns in q and k, bias [16, K, Kp], of all of which the first n rows / columns are real and the rest is never read.  Returns
+  (out, recorded |max| of out): out[i, h, :] = sum_j softmax_j(q_h[i] . k_h[j] / sqrt(D / 16) + bias[h, i, j]) v[j, :] for i < n
+  and zeros for n <= i < K.  out_init (flat, at least K * 16 * D floats; default zeros of exactly that size) is the buffer the
+  kernel writes into: the flat result comes back whole, so that a caller can see that nothing past [K,16,D] changed."""
+  lib = _L(lib)
+  q = f32(q); k = f32(k); v = f32(v); bias = f32(bias)
+  K, D = q.shape
+  assert k.shape == (K, D) and v.shape == (K, D) and bias.shape == (16, K, (K + 3) // 4 * 4)
+  out = np.zeros(K * 16 * D, np.float32) if out_init is None else f32(out_init).reshape(-1).copy()
+  amax = np.zeros(1, np.float32)
+  lib.check(lib.dll.odt_op_relation_attention(device, fptr(q), fptr(k), fptr(v), fptr(bias), K, D, int(n), fptr(out), out.size,
+                                              fptr(amax)))
+  return (out.reshape(K, 16, D) if out_init is None else out), float(amax[0])
+
+
 def se_tail(t2, w3, b3, fc1, fc2, shortcut, lib=None, device=0):
   """The tail of an SE bottleneck (reference nn.py:502-521) as the plan runs it: pool of t2 [B,H,W,ch] -> gate (conv3 + BN
   folded into fc1 = (W [4 ch, ch / 4], b), fc2 = (W [ch / 4, 4 ch], b)) -> conv3 (w3 [ch, 4 ch] with BN folded, + b3) ->

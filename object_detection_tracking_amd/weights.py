@@ -76,6 +76,24 @@ def conv_head_variables(config):
   return out + ["fastrcnn/fc/W", "fastrcnn/fc/b"]
 
 
+RELATION_SCOPES = ("fastrcnn/RM_r1", "fastrcnn/RM_r2")
+RELATION_VARIABLES = ("geo_emb/W", "geo_emb/b", "geo_conv/W", "geo_conv/b", "query_linear/W", "key_linear/W", "output_linear/W")
+
+
+# standard deviations of the synthetic relation variables (query / key / output: times 1 / sqrt(fan-in))
+RELATION_SCALES = {"geo_emb/W": 0.5, "geo_emb/b": 0.1, "geo_conv/W": 0.25, "geo_conv/b": 0.1, "query_linear/W": 1.0,
+                   "key_linear/W": 1.0, "output_linear/W": 1.0}
+
+
+def relation_variables(config):
+  """Names of the variables an --add_relation_nn graph needs on top of the 2-FC head, in execution order (reference
+  relation_network, nn.py:115-190, under fastrcnn/RM_r1 and fastrcnn/RM_r2: models.py:1044-1054): geo_emb/{W [4,64], b},
+  geo_conv/{W [1,1,64,16], b}, query_linear/W and key_linear/W [D,D], output_linear/W [16 D,D].  [] without the flag."""
+  if not getattr(config, "add_relation_nn", False):
+    return []
+  return [s + "/" + v for s in RELATION_SCOPES for v in RELATION_VARIABLES]
+
+
 def backbone_conv_specs(config):
   """Yield (scope, kh, cin, cout, has_bn, has_bias) for every conv on the path,
   in execution order (reference nn.py:843-1014, models.py:979-1009); cin is W's third dimension -- the channels per
@@ -249,6 +267,22 @@ def synthetic_weights(config, seed=0):
       cin = dc
     w["fastrcnn/fc/W"] = h_rng.standard_normal((dc * 49, dim), dtype=np.float32) * np.float32(np.sqrt(2.0 / (dc * 49)))
     w["fastrcnn/fc/b"] = h_rng.standard_normal((dim,), dtype=np.float32) * np.float32(0.02)
+  if getattr(config, "add_relation_nn", False):
+    # --add_relation_nn (nn.py:115-190) from a generator of its own.  The scales make the attention informative on the synthetic
+    # frames (tests/relation_reference.py asserts it on the reference alone): geo_conv spreads a[i,j,h] around zero, so that about
+    # half of the pairs pass the ReLU and the rest sit at the log(1e-6) floor; query / key give logits of a few units over the
+    # post-ReLU features (|h6|, |h7| ~ sqrt(D) on these weights), so that a softmax row is neither uniform nor one-hot;
+    # output_linear keeps RM at the size of its input
+    r_rng = np.random.default_rng([seed, 10])
+    for scope in RELATION_SCOPES:
+      w[scope + "/geo_emb/W"] = r_rng.standard_normal((4, 64), dtype=np.float32) * np.float32(RELATION_SCALES["geo_emb/W"])
+      w[scope + "/geo_emb/b"] = r_rng.standard_normal((64,), dtype=np.float32) * np.float32(RELATION_SCALES["geo_emb/b"])
+      w[scope + "/geo_conv/W"] = r_rng.standard_normal((1, 1, 64, 16), dtype=np.float32) * np.float32(RELATION_SCALES["geo_conv/W"])
+      w[scope + "/geo_conv/b"] = r_rng.standard_normal((16,), dtype=np.float32) * np.float32(RELATION_SCALES["geo_conv/b"])
+      for v in ("query_linear/W", "key_linear/W"):
+        w[scope + "/" + v] = r_rng.standard_normal((dim, dim), dtype=np.float32) * np.float32(RELATION_SCALES[v] / np.sqrt(dim))
+      w[scope + "/output_linear/W"] = r_rng.standard_normal((16 * dim, dim), dtype=np.float32) * np.float32(
+          RELATION_SCALES["output_linear/W"] / np.sqrt(16.0 * dim))
   return w
 
 

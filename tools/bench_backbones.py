@@ -26,6 +26,13 @@ python tools/bench_backbones.py --backbones r101,r101_convhead,r50_gn,r50_gn_con
   of 7 x 7) against their FLOP at the sustained rate of the fp16x2 kernels, and under --use_gn the four ROI GroupNorms
   (csrc/group_norm_roi.hip: one launch, one pass each) against the byte floor describe() computes from the plan's own tensors --
   one read and one write -- over the measured copy rate.
+python tools/bench_backbones.py --graph single --batch 1 --backbones r101,r101_relation [--topk 1000]
+  The relation-network box head (--add_relation_nn: RM_r1 behind fc6, RM_r2 behind fc7) next to the plain 2-FC head on the
+  single-image graph, in one run: profiles/relation_b1_1080p.txt.  A profiled pass times, per module, the geometric-bias kernel
+  and the attention kernel (csrc/relation.hip) and the Q | K and output_linear GEMMs, each next to a floor from the plan's own
+  shapes: the two attention products (2 K^2 D + 32 K^2 D FLOP) at the exact-f32 MFMA rate, the GEMMs at the rate the fp16x2
+  kernels sustain, the bias kernel's K^2 (64 tanh + 1280 FMA) at one v_fma_f32 per lane and clock, a tanh counted as 8 of them
+  (an exp and a reciprocal at quarter rate).
 One JSON line per backbone, and one with all of them at the end."""
 import argparse, json, os, subprocess, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -34,11 +41,14 @@ import numpy as np
 COPY_RATE = 6.29e12      # bytes/s, the project's measured device copy rate
 F32_MFMA_RATE = 155e12   # FLOP/s, v_mfma_f32_16x16x4_f32 back to back on every SIMD
 H2_RATE = 341e12         # FLOP/s of f32 work the fp16x2 conv kernels sustain over the R101 step (README.md)
+VEC_FMA_RATE = 256 * 64 * 2.4e9      # v_fma_f32 per second: 256 CUs x 64 lanes x 2.4 GHz
+TANH_FMA_SLOTS = 8       # issue slots of a tanhf counted in v_fma_f32: v_exp_f32 + v_rcp_f32 at quarter rate, nothing else
 BACKBONES = {"r101": {}, "resnext101": dict(use_resnext=True), "resnet34": dict(resnet34=True), "resnet18": dict(resnet18=True),
              "r101_nodil": dict(use_dilations=False), "r101_deformable": dict(use_dilations=False, use_deformable=True),
              "r50_gn": dict(resnet50=True, use_gn=True), "r101_gn": dict(use_gn=True),
              "r101_convhead": dict(use_conv_frcnn_head=True), "r50_gn_convhead": dict(resnet50=True, use_gn=True, use_conv_frcnn_head=True),
-             "r101_gn_convhead": dict(use_gn=True, use_conv_frcnn_head=True)}
+             "r101_gn_convhead": dict(use_gn=True, use_conv_frcnn_head=True),
+             "r101_relation": dict(add_relation_nn=True)}
 DEFAULT = ("r101", "resnext101", "resnet34", "resnet18")   # what a run without --backbones measures (profiles/backbones_b8_1080p.txt)
 
 
@@ -82,7 +92,7 @@ def child(a, name):
   frames = [synthetic_frames(B, H, W, seed=1234 + 77 * r) for r in range(max(1, a.rotate))]
   dev = [torch.from_numpy(f).cuda(a.device) for f in frames]
   torch.cuda.synchronize()
-  m = models.get_model(cfg, a.device, weights=weights, is_multi=True)
+  m = models.get_model(cfg, a.device, weights=weights, is_multi=a.graph == "multi")
   e = m.engine(B, H, W)
   e.forward_device_async(dev[0].data_ptr(), ODT_DTYPE_U8); e.synchronize()      # bring-up: the range guard's comparison
   k = [0]
@@ -154,6 +164,26 @@ def child(a, name):
       res["roi_group_norm"] = {"layers": dp["roi_group_norms"], "ms_per_step": dp["roi_group_norm_profiled_ms"] / n,
                                "bytes_per_step": dp["roi_group_norm_floor_bytes"],
                                "floor_ms_bytes_over_copy_rate": dp["roi_group_norm_floor_bytes"] / COPY_RATE * 1e3}
+  if d.get("relation_modules", 0) > 0:
+    e.profile(True)
+    run(a.steps)
+    dp = e.describe()
+    layers = {nm.split("[")[0]: (fl, ms) for nm, fl, ms, _ in e.profile_layers() if "/RM_r" in nm}
+    e.profile(False)
+    n = max(1, dp["profiled_forwards"])
+    K, D = a.topk, int(cfg.fpn_frcnn_fc_head_dim)
+    att_fl = B * (2.0 * K * K * D + 32.0 * K * K * D)
+    geo_fma, geo_tanh = B * K * K * (4 * 64 + 64 * 16), B * K * K * 64
+    res["relation"] = []
+    for i, scope in enumerate(("fastrcnn/RM_r1", "fastrcnn/RM_r2")):
+      qk, ol = layers[scope + "/query_key_linear"], layers[scope + "/output_linear"]
+      res["relation"].append({
+          "module": scope, "geo_ms": dp["relation_geo_profiled_ms"][i] / n, "geo_fma": geo_fma, "geo_tanh": geo_tanh,
+          "geo_floor_ms": (geo_fma + TANH_FMA_SLOTS * geo_tanh) / VEC_FMA_RATE * 1e3,
+          "attention_ms": dp["relation_attention_profiled_ms"][i] / n, "attention_flop": att_fl,
+          "attention_floor_ms": att_fl / F32_MFMA_RATE * 1e3,
+          "qk_ms": qk[1] / n, "qk_flop": qk[0], "qk_floor_ms": qk[0] / H2_RATE * 1e3,
+          "output_linear_ms": ol[1] / n, "output_linear_flop": ol[0], "output_linear_floor_ms": ol[0] / H2_RATE * 1e3})
   m.close()
   print(json.dumps(res), flush=True)
   return res
@@ -172,6 +202,7 @@ def main():
   ap.add_argument("--only", default="", choices=[""] + sorted(BACKBONES))
   ap.add_argument("--backbones", default="", help="comma-separated subset of %s (default: %s)" % (", ".join(BACKBONES), ",".join(DEFAULT)))
   ap.add_argument("--device", type=int, default=0)
+  ap.add_argument("--graph", default="multi", choices=["multi", "single"], help="Mask_RCNN_FPN_multi (default) or the single-image Mask_RCNN_FPN")
   a = ap.parse_args()
   if a.only:
     child(a, a.only)
@@ -182,7 +213,7 @@ def main():
     if name not in BACKBONES:
       sys.exit("unknown backbone %s" % name)
     cmd = [sys.executable, os.path.abspath(__file__), "--only", name] + \
-        [x for k in ("batch", "height", "width", "topk", "steps", "warmup", "rounds", "rotate", "device") for x in ("--" + k, str(getattr(a, k)))]
+        [x for k in ("batch", "height", "width", "topk", "steps", "warmup", "rounds", "rotate", "device", "graph") for x in ("--" + k, str(getattr(a, k)))]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
     if r.returncode != 0:
       sys.exit("%s: child exited with %d" % (name, r.returncode))
@@ -217,6 +248,12 @@ def main():
       print("            ROI GroupNorm: %d layers, %.3f ms/step measured;  floor from the plan's tensors (one read + one write): %.2f GB -> "
             "%.3f ms at %.2f TB/s (measured / floor %.2f)" % (g["layers"], g["ms_per_step"], g["bytes_per_step"] / 1e9,
             g["floor_ms_bytes_over_copy_rate"], COPY_RATE / 1e12, g["ms_per_step"] / g["floor_ms_bytes_over_copy_rate"]))
+    for g in res.get("relation", []):
+      print("            %s: bias %.3f ms (floor %.3f: %.0f M tanh + %.0f M FMA), attention %.3f ms (floor %.3f: %.1f GFLOP at %.0f TF), "
+            "Q|K %.3f ms (floor %.3f), output_linear %.3f ms (floor %.3f: %.1f GFLOP at %.0f TF)" % (
+                g["module"].split("/")[-1], g["geo_ms"], g["geo_floor_ms"], g["geo_tanh"] / 1e6, g["geo_fma"] / 1e6, g["attention_ms"],
+                g["attention_floor_ms"], g["attention_flop"] / 1e9, F32_MFMA_RATE / 1e12, g["qk_ms"], g["qk_floor_ms"],
+                g["output_linear_ms"], g["output_linear_floor_ms"], g["output_linear_flop"] / 1e9, H2_RATE / 1e12))
   print(json.dumps(out), flush=True)
 
 
