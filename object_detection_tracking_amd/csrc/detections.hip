@@ -7,6 +7,9 @@
 //   ODT_GRAPH_MULTI : fastrcnn_predictions_multibatch :2924-2976
 //                     (combined_non_max_suppression, score_threshold = -inf, zero-padded
 //                     slots of the other images are legal candidates).
+// TF admits an NMS candidate only if score > score_threshold (strict).  The scores here are softmax outputs
+// (head_post_kernel: exp(x - max) * (1 / sum), in [0, 1]), so none is -inf and the rule drops nothing at the -inf
+// threshold; write_class_list relies on scores >= 0 as well.  (proposals.hip, whose scores are raw logits, applies it.)
 // Canonical tie orders are those of oracle/tfops.py.  One 1024-thread workgroup per
 // (class, image) for the NMS, one per image for the final selection.
 #include "odt_common.hpp"

@@ -6,6 +6,10 @@
 //   ODT_GRAPH_MULTI : generate_rpn_proposals_multibatch + the zero-padded merge and the
 //                     area > 0 filter (reference nn.py:1406-1482, models.py:2458-2522)
 //
+// Both graphs call TF's NMS with the default score_threshold, -inf, and TF admits a candidate only if
+// score > score_threshold (strict): an anchor whose logit is -inf takes a top-k slot but is never proposed.  The NMS
+// kernels cut their score-sorted candidates to those above -inf (select_device.hpp, count_above_neg_inf).
+//
 // One 1024-thread workgroup per (image, level) for select + decode, one for NMS, one per image
 // for the merge; everything stays in LDS, counts stay on the device (no host sync).  K <= 1024 (every
 // configuration the reference ships; the script default is 1000) takes the one-candidate-per-thread
@@ -123,13 +127,22 @@ __global__ void __launch_bounds__(kSelThreads) rpn_select_kernel(ProposalParams 
 }
 
 // ---- stage B: NMS per (image, level) ----------------------------------------------------
+// (cand_scores of a level descend: rpn_select_kernel compacts in top-k order.  The candidates with a -inf logit are cut
+// here, where TF cuts them -- select_device.hpp, count_above_neg_inf)
+struct PlainScoreAt {
+  const float* base;
+  __device__ __forceinline__ float operator()(int e) const { return base[e]; }
+};
 __global__ void __launch_bounds__(kSelThreads) rpn_nms_kernel(ProposalParams p) {
   __shared__ NmsScratch s;
+  __shared__ int s_n;
   const int l = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const size_t o = ((size_t)b * p.nlevels + l) * p.K;
-  const int n = p.cand_count[b * p.nlevels + l];
-  for (int i = tid; i < n * 4; i += blockDim.x) s.box[i] = p.cand_boxes[o * 4 + i];
+  const int nc = p.cand_count[b * p.nlevels + l];
+  count_above_neg_inf(PlainScoreAt{p.cand_scores + o}, nc, &s_n);
+  for (int i = tid; i < nc * 4; i += blockDim.x) s.box[i] = p.cand_boxes[o * 4 + i];
   __syncthreads();
+  const int n = s_n;
   block_nms(n, p.K, p.nms_thresh, s);
   const int nk = s.nkeep;
   for (int i = tid; i < nk; i += blockDim.x) {
@@ -151,10 +164,13 @@ struct CandBoxAt {
 };
 __global__ void __launch_bounds__(kSelThreads) rpn_nms_big_kernel(ProposalParams p) {
   __shared__ __attribute__((aligned(16))) char raw[sizeof(NmsBigScratch)];
+  __shared__ int s_n;
   NmsBigScratch& s = *reinterpret_cast<NmsBigScratch*>(raw);
   const int l = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const size_t o = ((size_t)b * p.nlevels + l) * p.K;
-  const int n = p.cand_count[b * p.nlevels + l];
+  count_above_neg_inf(PlainScoreAt{p.cand_scores + o}, p.cand_count[b * p.nlevels + l], &s_n);
+  __syncthreads();
+  const int n = s_n;
   block_nms_paneled(n, p.K, p.nms_thresh, CandBoxAt{p.cand_boxes + o * 4}, s);
   const int nk = s.nkeep;
   for (int i = tid; i < nk; i += blockDim.x) {
@@ -264,10 +280,6 @@ __global__ void __launch_bounds__(kSelThreads) rpn_merge_kernel(ProposalParams p
 }
 
 // ---- stand-alone top-k / NMS (parity entry points) ---------------------------------------
-struct PlainScoreAt {
-  const float* base;
-  __device__ __forceinline__ float operator()(int e) const { return base[e]; }
-};
 template <class Scratch>
 __global__ void __launch_bounds__(kSelThreads) topk_kernel(const float* scores, int n, int k,
                                                            int* idx_out) {
@@ -277,6 +289,11 @@ __global__ void __launch_bounds__(kSelThreads) topk_kernel(const float* scores, 
   for (int t = threadIdx.x; t < k; t += blockDim.x) idx_out[t] = (int)key64_index(s.keys_b[t]);
 }
 
+struct OrderedScoreAt {
+  const float* scores;
+  const int* order;      // LDS: sorted position -> original index
+  __device__ __forceinline__ float operator()(int i) const { return scores[order[i]]; }
+};
 __global__ void __launch_bounds__(kSelThreads) nms_kernel(const float* boxes, const float* scores,
                                                           int n, int max_out, float thresh,
                                                           int* idx_out, int* n_out) {
@@ -298,12 +315,14 @@ __global__ void __launch_bounds__(kSelThreads) nms_kernel(const float* boxes, co
   __syncthreads();
   const int src = (tid < n) ? order[tid] : 0;   // sorted position tid -> original index
   __shared__ int s_orig[kMaxTopK];
+  __shared__ int s_n;
   if (tid < n) s_orig[tid] = src;
   __syncthreads();                               // keys/order (aliasing the bitmask) are dead now
+  count_above_neg_inf(OrderedScoreAt{scores, s_orig}, n, &s_n);   // score > -inf: TF's candidate rule
   if (tid < n)
     for (int q = 0; q < 4; ++q) s.box[tid * 4 + q] = boxes[src * 4 + q];
   __syncthreads();
-  block_nms(n, max_out, thresh, s);
+  block_nms(s_n, max_out, thresh, s);
   const int nk = s.nkeep;
   for (int i = tid; i < nk; i += blockDim.x) idx_out[i] = s_orig[s.keep[i]];
   if (tid == 0) *n_out = nk;
@@ -324,6 +343,7 @@ __global__ void __launch_bounds__(kSelThreads) nms_big_kernel(const float* boxes
                                                               int* idx_out, int* n_out) {
   __shared__ __attribute__((aligned(16))) char raw[sizeof(NmsBigScratch)];
   __shared__ int s_orig[kMaxTopKBig];
+  __shared__ int s_n;
   NmsBigScratch& s = *reinterpret_cast<NmsBigScratch*>(raw);
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(s.kbox);     // 32 KiB of the 64: dead before the walk
   const int tid = threadIdx.x;
@@ -336,7 +356,9 @@ __global__ void __launch_bounds__(kSelThreads) nms_big_kernel(const float* boxes
     s_orig[rank] = t;
   }
   __syncthreads();
-  block_nms_paneled(n, max_out, thresh, OrderedBoxAt{boxes, s_orig}, s);
+  count_above_neg_inf(OrderedScoreAt{scores, s_orig}, n, &s_n);
+  __syncthreads();
+  block_nms_paneled(s_n, max_out, thresh, OrderedBoxAt{boxes, s_orig}, s);
   const int nk = s.nkeep;
   for (int i = tid; i < nk; i += blockDim.x) idx_out[i] = s_orig[s.keep[i]];
   if (tid == 0) *n_out = nk;

@@ -5,6 +5,9 @@
 //   * block_nms          -- tf.image.non_max_suppression on <= 1024 score-sorted boxes:
 //                           upper-triangular 64-bit suppression bitmask in LDS (parallel IoUs),
 //                           then one wave walks the candidates in order.
+//   * block_nms_paneled  -- the same over up to 4096 boxes, in panels of 512
+//   * count_above_neg_inf -- TF's candidate rule, score > score_threshold = -inf (strict): the callers cut the
+//                           score-sorted candidates to those above -inf before either walk
 // These restate the semantics pinned in oracle/tfops.py (TF-1.15 top_k / NMS kernels).
 // All arithmetic is fp32 with one rounding per operation (build uses -ffp-contract=off) so
 // that on identical inputs the selected indices are bit-identical to the oracle's.
@@ -177,8 +180,20 @@ __device__ __forceinline__ bool iou_gt(const float* bi, float area_i, const floa
   return iou > thresh;
 }
 
+// TF's NMS kernels admit a candidate only if score > score_threshold, strictly, and every call site of the reference
+// leaves the threshold at its default, -inf: a -inf score is no candidate.  Candidates reach the walks below sorted by
+// descending score, so the -inf ones are a suffix and the rule is a shorter n: *out gets the number of score_at(0..n-1)
+// above -inf.  Exactly one thread writes it (NaN scores are outside the contract); the caller's next barrier publishes it.
+template <class ScoreAt>
+__device__ __forceinline__ void count_above_neg_inf(ScoreAt score_at, int n, int* out) {
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  if (tid == 0 && (n == 0 || !(score_at(0) > -INFINITY))) *out = 0;
+  for (int i = tid; i < n; i += nthr)
+    if (score_at(i) > -INFINITY && (i + 1 == n || !(score_at(i + 1) > -INFINITY))) *out = i + 1;
+}
+
 // Boxes must already be in s.box (any consistent axis order) for candidates 0..n-1, sorted by
-// descending score.  Fills s.keep[0..s.nkeep) with the selected candidate positions.
+// descending score with score > -inf (count_above_neg_inf).  Fills s.keep[0..s.nkeep) with the selected candidate positions.
 __device__ inline void block_nms(int n, int max_out, float thresh, NmsScratch& s) {
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int nw = (n + 63) >> 6;
