@@ -1,6 +1,7 @@
 // libodt_hip.so -- host-side model of a handle: the static execution plan (ops, conv records, tensors), its memory
 // (weights, activation arena, workspaces, ingest slots) and the helpers shared by the plan builders (plan_common.hip,
-// plan_fpn.hip, plan_effdet.hip), the runtime (runtime.hip) and the stand-alone op entry points (op_shims.hip).
+// plan_fpn.hip, plan_effdet.hip), the runtime (runtime.hip) and the stand-alone op entry points (op_shims.hpp, op_shims.hip,
+// op_shims_conv.hip).
 // Host code only; every device kernel lives in the kernel translation units (conv_*.hip, proposals.hip, ...).
 #pragma once
 #include "../../include/odt.h"

@@ -24,7 +24,7 @@
 // T = 64 x budget 5, N = 100: 11 workgroups of 4 waves (one per 32 detections) instead of 512, no shuffle trees.
 #include <cstring>
 
-#include "odt_common.hpp"
+#include "op_shims.hpp"
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -264,3 +264,27 @@ int CosineCtx::run(int dev, const float* const* gal_rows, int G, const int* seg,
 }
 
 }  // namespace odt
+
+using namespace odt;
+
+extern "C" int odt_nn_cosine(int device, const float* gallery, const int32_t* seg_offsets, int T, const float* dets,
+                             int N, int D, double* cost) {
+  ODT_CHECK(T >= 0 && N >= 0 && D > 0, "odt_nn_cosine: bad sizes");
+  if (T == 0 || N == 0) return 0;
+  ODT_CHECK(gallery && seg_offsets && dets && cost, "odt_nn_cosine: null argument");
+  if (set_dev(device)) return 1;
+  const int G = seg_offsets[T];
+  ODT_CHECK(G > 0 && seg_offsets[0] == 0, "odt_nn_cosine: bad segment offsets");
+  for (int t = 0; t < T; ++t) ODT_CHECK(seg_offsets[t + 1] > seg_offsets[t], "odt_nn_cosine: empty track gallery");
+  // persistent per-device scratch + its own stream (no allocation, no null stream, no device-wide sync per call)
+  static std::mutex mu;
+  static std::map<int, std::unique_ptr<CosineCtx>> ctxs;
+  std::lock_guard<std::mutex> lk(mu);
+  const int dev = device;
+  std::unique_ptr<CosineCtx>& cx = ctxs[dev];
+  if (!cx) cx.reset(new CosineCtx());
+  std::vector<const float*> gr(G), dr(N);
+  for (int g = 0; g < G; ++g) gr[g] = gallery + (size_t)g * D;
+  for (int j = 0; j < N; ++j) dr[j] = dets + (size_t)j * D;
+  return cx->run(dev, gr.data(), G, seg_offsets, T, dr.data(), N, D, cost);
+}
