@@ -133,6 +133,14 @@ typedef struct odt_config {
                              * variables fastrcnn/RM_r{1,2}/{geo_emb/{W [4,64], b}, geo_conv/{W [1,1,64,16], b}, query_linear/W,
                              * key_linear/W [D,D], output_linear/W [16 D, D]} (csrc/relation.hip).  Single-image graph (every image
                              * of a batch on its own), rpn_topk <= 1024, head_dim a multiple of 64 up to 1024; not with use_conv_frcnn_head */
+  int32_t use_att_frcnn_head; /* --use_att_frcnn_head (fastrcnn_2fc_head, models.py:1064-1089): behind whichever hidden vector the box
+                             * head produced (fc7, RM_r2 or fastrcnn/fc), hidden' = hidden + relu(attended fastrcnn/att_trans/{W
+                             * [fpn_channels, head_dim], b}) feeds the output layers; attended [R, fpn_channels] is the sum over the RoI's
+                             * 49 positions of feature * attention.  The reference's attention map is a softmax over an axis of ONE
+                             * channel -- 1.0 for every finite logit -- so the device adds the 49 positions (csrc/att_head.hip) and does
+                             * not evaluate that conv: fastrcnn/attention/{W [3,3,fpn_channels,1], b [1]} must be present, of those
+                             * shapes and finite, and cannot influence the output.  Both graphs, any backbone and box head; with or
+                             * without add_mask */
 } odt_config;
 
 /* conv_arith: all modes keep f32 tensors and f32 accumulation.  ODT_ARITH_F32: every product on the exact-f32 MFMA
@@ -574,6 +582,12 @@ int odt_op_relation_geo(int device, const float* boxes, int K, int n, const floa
  * amax [1]: the |max| the kernel recorded for out. */
 int odt_op_relation_attention(int device, const float* q, const float* k, const float* v, const float* bias, int K, int D, int n,
                               float* out, size_t out_elems, float* amax);
+/* The two kernels of the box head's attention branch (csrc/att_head.hip; --use_att_frcnn_head) as the plan runs them.  Pool: x [R,49,C]
+ * (C % 4 == 0) -> out [R,C], out[r][c] = x[r][0][c] + x[r][1][c] + ... + x[r][48][c] added in that order in f32.  amax [1]: the |max| the
+ * kernel recorded for out. */
+int odt_op_att_pool(int device, const float* x, int R, int C, float* out, float* amax);
+/* ... add: out [R,D] = h [R, D at row pitch ldh] + a [R,D] (D % 4 == 0, ldh % 4 == 0, ldh >= D); amax [1] likewise. */
+int odt_op_att_add(int device, const float* h, int ldh, const float* a, int R, int D, float* out, float* amax);
 /* BiFPN node input fusion (launch_bifpn_fuse): n = 1..3 inputs ins[k] [B,in_hw[k][0],in_hw[k][1],ldc], mode[k] 0 same
  * size, 1 nearest resize, 2 3x3 / s2 'SAME' max pool with pads[k] = (top, left); wsm != NULL: 'fastattn' with the raw
  * WSM scalars [n], else a plain sum; act 0 / 2 (swish).  out [B,h,w,ldc]. */

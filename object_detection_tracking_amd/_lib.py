@@ -51,6 +51,7 @@ class OdtConfig(C.Structure):
       ("use_conv_frcnn_head", C.c_int32),      # the 4-conv + FC box head (fastrcnn/conv0..3, fastrcnn/fc)
       ("conv_head_dim", C.c_int32),            # conv_frcnn_head_dim (256)
       ("add_relation_nn", C.c_int32),          # relation modules RM_r1 / RM_r2 in the 2-FC box head
+      ("use_att_frcnn_head", C.c_int32),       # hidden + relu(att_trans(sum of the RoI's 49 positions)) in front of the output layers
   ]
 
 
@@ -114,7 +115,7 @@ class OdtLib(object):
       "odt_op_bottleneck_tail", "odt_op_bottleneck_block", "odt_op_stem", "odt_op_conv_choice", "odt_op_last_conv", "odt_op_preprocess",
       "odt_op_maxpool", "odt_op_topk", "odt_op_nms", "odt_op_proposals",
       "odt_op_roi_align", "odt_op_roi_align_plan", "odt_op_mask_select", "odt_op_detections", "odt_op_class_nms",
-      "odt_op_dwconv", "odt_op_se_gate", "odt_op_rse_gate", "odt_op_rse_apply", "odt_op_se_tail", "odt_op_group_conv", "odt_op_deform_conv", "odt_op_deform_conv_view", "odt_op_group_norm", "odt_op_group_norm_roi", "odt_op_relation_geo", "odt_op_relation_attention", "odt_op_bifpn_fuse", "odt_op_mbconv_expand_dw", "odt_op_effdet_post",
+      "odt_op_dwconv", "odt_op_se_gate", "odt_op_rse_gate", "odt_op_rse_apply", "odt_op_se_tail", "odt_op_group_conv", "odt_op_deform_conv", "odt_op_deform_conv_view", "odt_op_group_norm", "odt_op_group_norm_roi", "odt_op_relation_geo", "odt_op_relation_attention", "odt_op_att_pool", "odt_op_att_add", "odt_op_bifpn_fuse", "odt_op_mbconv_expand_dw", "odt_op_effdet_post",
       "odt_op_preprocess_rgb", "odt_forward_serial", "odt_mask_rle", "odt_op_mask_rle", "odt_tracker_create", "odt_tracker_destroy",
       "odt_tracker_predict", "odt_tracker_update", "odt_tracker_tracks", "odt_lsap", "odt_tracker_nms",
       "odt_tmot_create", "odt_tmot_destroy", "odt_tmot_reset", "odt_tmot_update", "odt_tmot_tracks",
@@ -221,6 +222,8 @@ class OdtLib(object):
     d.odt_op_group_norm_roi.argtypes = [C.c_int, c_float_p] + [C.c_int] * 5 + [c_float_p, c_float_p, C.c_float] + [c_float_p] * 4
     d.odt_op_relation_geo.argtypes = [C.c_int, c_float_p, C.c_int, C.c_int, c_float_p, c_float_p]
     d.odt_op_relation_attention.argtypes = [C.c_int] + [c_float_p] * 4 + [C.c_int] * 3 + [c_float_p, C.c_size_t, c_float_p]
+    d.odt_op_att_pool.argtypes = [C.c_int, c_float_p, C.c_int, C.c_int, c_float_p, c_float_p]
+    d.odt_op_att_add.argtypes = [C.c_int, c_float_p, C.c_int, c_float_p, C.c_int, C.c_int, c_float_p, c_float_p]
     d.odt_op_bifpn_fuse.argtypes = [C.c_int, C.c_int, C.POINTER(c_float_p), c_int_p, c_int_p, c_int_p, c_float_p] + \
         [C.c_int] * 5 + [c_float_p]
     d.odt_op_mbconv_expand_dw.argtypes = [C.c_int, c_float_p] + [C.c_int] * 4 + [c_float_p] * 2 + [C.c_int] * 2 + \

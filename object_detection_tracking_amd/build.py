@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["runtime.hip", "plan_common.hip", "plan_fpn.hip", "plan_effdet.hip", "op_shims.hip", "op_shims_conv.hip", "conv_igemm.hip", "conv_split.hip", "conv_split1.hip", "conv_split3.hip", "conv_h2.hip", "conv_h2d.hip", "conv_h2k.hip", "conv_block.hip", "conv_stem.hip", "elementwise.hip", "proposals.hip",
-           "roi_align.hip", "detections.hip", "tracker.hip", "tracker_core.cpp", "knobs.cpp", "effnet.hip", "effnet_mbconv.hip", "resnet_se.hip", "conv_group.hip", "conv_deform.hip", "group_norm.hip", "group_norm_roi.hip", "relation.hip", "effdet_post.hip", "mask_rle.hip", "probe.hip"]
+           "roi_align.hip", "detections.hip", "tracker.hip", "tracker_core.cpp", "knobs.cpp", "effnet.hip", "effnet_mbconv.hip", "resnet_se.hip", "conv_group.hip", "conv_deform.hip", "group_norm.hip", "group_norm_roi.hip", "relation.hip", "att_head.hip", "effdet_post.hip", "mask_rle.hip", "probe.hip"]
 HEADERS = ["odt_common.hpp", "knobs.hpp", "odt_model.hpp", "op_shims.hpp", "conv_split_common.hpp", "conv_split_epilogue.hpp", "conv_h2f_tail.hpp", "select_device.hpp", os.path.join(ROOT, "include", "odt.h")]
 LIB_HIP = os.path.join(HERE, "libodt_hip.so")
 LIB_EMU = os.path.join(ROOT, "tests", "emu", "libodt_emu.so")

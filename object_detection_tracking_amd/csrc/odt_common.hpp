@@ -539,6 +539,27 @@ struct RelationAttnParams {
 };
 int launch_relation_attention(const RelationAttnParams& p, hipStream_t stream);
 
+// ------------------------------------------------------- attention branch of the box head (att_head.hip; --use_att_frcnn_head)
+// The two kernels around fastrcnn/att_trans (reference models.py:1064-1089); plain f32 in every arithmetic mode.  Every pointer
+// 16-byte aligned.
+// pool: x [R, 49, C] dense, C % 4 == 0 -> out [R, C], the 49 positions of a RoI added one after another in (h, w) order
+struct AttPoolParams {
+  const float* x;        // [R, 49, C]
+  float* out;            // [R, C]
+  unsigned* amax;        // range slot of out (|max| of what is stored) or nullptr
+  int R, C;
+};
+int launch_att_pool(const AttPoolParams& p, hipStream_t stream);
+// add: out [R, D] = h [R, D at row pitch ldh] + a [R, D]; D % 4 == 0, ldh % 4 == 0, ldh >= D
+struct AttAddParams {
+  const float* h;        // [R, D] at pitch ldh
+  const float* a;        // [R, D]
+  float* out;            // [R, D]
+  unsigned* amax;        // range slot of out or nullptr
+  int R, D, ldh;
+};
+int launch_att_add(const AttAddParams& p, hipStream_t stream);
+
 // ------------------------------------------------------- EfficientDet tail (effdet_post.hip)
 struct EffPostParams {
   const float* cls[5];     // per level [B, npix, ldc_cls]  (9 * ncls valid channels: anchor-major)

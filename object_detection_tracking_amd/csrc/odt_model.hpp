@@ -62,7 +62,7 @@ struct ConvOp {
 enum OpKind { OP_PRE, OP_CONV, OP_POOL, OP_SUB2, OP_PROPOSALS, OP_ROI_HEAD, OP_DETECT, OP_ROI_FINAL,
               OP_ROI_MASK, OP_MASK_SELECT, OP_PRE_RGB, OP_DW, OP_CMEAN, OP_CSCALE, OP_FUSE, OP_EFF_POST, OP_ROI_EFF, OP_SE_GATE,
               OP_SE_GATE_MEAN, OP_WSCALE, OP_MB_EXPAND_DW, OP_RSE_GATE, OP_RSE_APPLY, OP_GCONV, OP_BLOCK, OP_DCONV, OP_GN, OP_GN_ROI,
-              OP_RELATION_GEO, OP_RELATION_ATTN };
+              OP_RELATION_GEO, OP_RELATION_ATTN, OP_ATT_POOL, OP_ATT_ADD };
 struct Op {
   OpKind kind;
   int conv = -1;        // index into convs (OP_BLOCK: the block's conv2, whose record launches conv_block_kernel)
@@ -84,6 +84,8 @@ struct Op {
   RoiGroupNormParams gnr{};   // OP_GN_ROI: GroupNorm behind a conv of the 4-conv box head, per ROI (group_norm_roi.hip)
   RelationGeoParams rg{};     // OP_RELATION_GEO: the geometric bias of a relation module (relation.hip)
   RelationAttnParams ra{};    // OP_RELATION_ATTN: its attention, softmax(Q K^T / sqrt(dh) + bias) V per head (relation.hip)
+  AttPoolParams ap{};         // OP_ATT_POOL: the 49-position sum of the RoI features in front of fastrcnn/att_trans (att_head.hip)
+  AttAddParams aa{};          // OP_ATT_ADD: hidden + relu(att_trans), the tensor fastrcnn/outputs reads (att_head.hip)
   float* aux = nullptr; // OP_CMEAN: means out [B,ldc]; OP_CSCALE / OP_WSCALE: gates in [B,ldc]
   const float* wt0 = nullptr;   // OP_WSCALE: the conv's unscaled weights [Cout][K] (conv = index of the conv whose weights are rebuilt)
   float* aux2 = nullptr;   // OP_CMEAN: partial-sum scratch
@@ -146,6 +148,8 @@ struct odt_model {
   int gn_ops = 0;                    // odt_config.use_gn: GroupNorm layers, three launches each (group_norm.hip)
   int gn_roi_ops = 0;                // odt_config.use_gn + use_conv_frcnn_head: ROI GroupNorm layers of the box head, one launch each (group_norm_roi.hip)
   int rel_modules = 0;               // odt_config.add_relation_nn: relation modules of the box head (RM_r1, RM_r2), two launches each (relation.hip)
+  int att_head = 0;                  // odt_config.use_att_frcnn_head: the box head runs OP_ATT_POOL, fastrcnn/att_trans and OP_ATT_ADD (att_head.hip)
+  int att_conv = -1;                 // ... index of fastrcnn/att_trans in convs (profiling: its time is the conv's)
   int mb_fused = 0;                  // EfficientNet: MBConv blocks whose expand + depthwise run as one kernel (effnet_mbconv.hip)
   // tail overlap: the selection / ROIAlign / box-head / NMS kernels of forward i (a few dozen workgroups each,
   // ~2 ms per 8-frame step) run on a side stream under the backbone of forward i+1.  The next forward's FPN stage
@@ -200,6 +204,8 @@ struct odt_model {
   double prof_gn_roi_ms = 0;
   std::vector<hipEvent_t> ev_rel;    // relation module i: events [4 i, 4 i + 3] (geo before / after, attention before / after)
   double prof_rel_geo_ms[2] = {0, 0}, prof_rel_attn_ms[2] = {0, 0};
+  std::vector<hipEvent_t> ev_att;    // the attention branch: events [0, 1] around OP_ATT_POOL, [2, 3] around OP_ATT_ADD
+  double prof_att_pool_ms = 0, prof_att_add_ms = 0;
   int prof_forwards = 0;
   int prof_launches = 0;
 
@@ -333,6 +339,8 @@ void visit_op_ptrs(odt_model* m, size_t oi, F&& f) {
     case OP_GN_ROI: f(op.gnr.x); f(op.gnr.out); break;      // (mean / var, where kept, are dedicated allocations)
     case OP_RELATION_GEO: f(op.rg.boxes); f(op.rg.bias); break;
     case OP_RELATION_ATTN: f(op.ra.q); f(op.ra.k); f(op.ra.v); f(op.ra.bias); f(op.ra.out); break;
+    case OP_ATT_POOL: f(op.ap.x); f(op.ap.out); break;
+    case OP_ATT_ADD: f(op.aa.h); f(op.aa.a); f(op.aa.out); break;
     case OP_FUSE: for (auto& p : op.fuse.in) f(p); f(op.fuse.out); break;
     case OP_EFF_POST: for (auto& p : m->eff_post.cls) f(p); for (auto& p : m->eff_post.box) f(p); break;
     case OP_CMEAN: case OP_CSCALE: case OP_SE_GATE: case OP_SE_GATE_MEAN: case OP_WSCALE: case OP_POOL: case OP_SUB2: break;

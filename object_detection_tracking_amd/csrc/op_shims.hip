@@ -595,6 +595,35 @@ int odt_op_relation_attention(int device, const float* q, const float* k, const 
   return get_dev(out, p.out, out_elems);
 }
 
+int odt_op_att_pool(int device, const float* x, int R, int C, float* out, float* amax) {
+  ODT_CHECK(x && out && amax, "odt_op_att_pool: null argument");
+  ODT_CHECK(R >= 1 && C >= 1 && (double)R * 49 * C < 1073741824.0, "odt_op_att_pool: bad sizes");
+  ODT_CHECK(C % 4 == 0, "odt_op_att_pool: C must be a multiple of 4 (C = " + std::to_string(C) + ")");
+  if (set_dev(device)) return 1;
+  GBufs g;
+  AttPoolParams p; std::memset(&p, 0, sizeof(p));
+  if (g.alloc("x", (size_t)R * 49 * C, &p.x, -1, x) || g.alloc("out", (size_t)R * C, &p.out) || alloc_amax(g, &p.amax)) return 1;
+  p.R = R; p.C = C;
+  if (launch_att_pool(p, nullptr) || g.check("odt_op_att_pool") || read_amax(p.amax, amax)) return 1;
+  return get_dev(out, p.out, (size_t)R * C);
+}
+
+int odt_op_att_add(int device, const float* h, int ldh, const float* a, int R, int D, float* out, float* amax) {
+  ODT_CHECK(h && a && out && amax, "odt_op_att_add: null argument");
+  ODT_CHECK(R >= 1 && D >= 1 && ldh >= 1 && (double)R * ldh < 1073741824.0 && (double)R * D < 1073741824.0, "odt_op_att_add: bad sizes");
+  ODT_CHECK(D % 4 == 0, "odt_op_att_add: D must be a multiple of 4 (D = " + std::to_string(D) + ")");
+  ODT_CHECK(ldh >= D && ldh % 4 == 0, "odt_op_att_add: ldh must be a multiple of 4 and at least D (ldh = " + std::to_string(ldh) + ", D = " +
+                                          std::to_string(D) + ")");
+  if (set_dev(device)) return 1;
+  GBufs g;
+  AttAddParams p; std::memset(&p, 0, sizeof(p));
+  if (g.alloc("h", (size_t)R * ldh, &p.h, -1, h) || g.alloc("a", (size_t)R * D, &p.a, -1, a) || g.alloc("out", (size_t)R * D, &p.out) ||
+      alloc_amax(g, &p.amax)) return 1;
+  p.R = R; p.D = D; p.ldh = ldh;
+  if (launch_att_add(p, nullptr) || g.check("odt_op_att_add") || read_amax(p.amax, amax)) return 1;
+  return get_dev(out, p.out, (size_t)R * D);
+}
+
 int odt_op_effdet_post(int device, int B, int ncls, const int32_t* npix, int ldc_cls, int ldc_box,
                        const float* const* cls, const float* const* box, const float* anchors, int k, int max_out,
                        float score_thresh, float iou_thresh, float image_scale, int32_t* cand_idx, float* cand_boxes,

@@ -414,6 +414,20 @@ int attach_split_weights(odt_model* m) {
       m->range_slot_name[slot] = op.rel == 0 ? "rm_r1_attn" : "rm_r2_attn";
       continue;
     }
+    if (op.kind == OP_ATT_POOL || op.kind == OP_ATT_ADD) {
+      // the attention branch of the box head, likewise: fastrcnn/att_trans reads the pooled RoI features, fastrcnn/outputs the sum
+      const bool pool = op.kind == OP_ATT_POOL;
+      const float* out = pool ? op.ap.out : op.aa.out;
+      slot_of.erase(out);
+      if (pol.family != 2) continue;
+      const int g = tail ? 1 : 0;
+      ODT_CHECK(m->amax_used[g] < odt_model::kAmaxSlots, "too many conv outputs for the range slots");
+      const int slot = (tail ? odt_model::kAmaxSlots : 0) + m->amax_used[g]++;
+      slot_of[out] = slot;
+      (pool ? m->ops[oi].ap.amax : m->ops[oi].aa.amax) = m->amax_dev + (size_t)slot * kAmaxWays;
+      m->range_slot_name[slot] = pool ? "att_pool" : "att_hidden";
+      continue;
+    }
     if (op.kind == OP_POOL || op.kind == OP_SUB2) {
       auto it = slot_of.find(op.in.d);
       if (it != slot_of.end()) slot_of[op.out.d] = it->second; else slot_of.erase(op.out.d);

@@ -185,6 +185,57 @@ int relation_module(odt_model* m, int index, const std::string& scope, const Ten
   return upload_conv_plain(m, scope + "/output_linear", 1, 1, kRelHeads * D, D, false, &co.wt, &co.bias) || add_conv(m, co, out);
 }
 
+// The attention branch of the box head (--use_att_frcnn_head; fastrcnn_2fc_head, models.py:1064-1089 and :2682-2707), behind
+// whichever `hidden` [1,1,B K,D] the configured head produced: out = hidden + relu(attended fastrcnn/att_trans/W + b), attended =
+// sum over the 49 positions of feature * attention.  The attention map is conv2d(..., activation = softmax) over ONE channel: 1.0f
+// for every finite logit, so the device sums the RoI features and does not evaluate that conv; fastrcnn/attention/{W,b} must be
+// there, of the graph's shapes and finite (a non-finite one gives NaN rows in the reference).  Three launches: OP_ATT_POOL over
+// `roi` (the [1,1,B K,49 FC] RoI features the head already read), att_trans as a 1x1 conv with bias and ReLU on the conv kernels,
+// OP_ATT_ADD -- the add sits behind the ReLU, so it is not a conv residual.  Stage names: att_pool, att_trans, att_hidden
+int attention_branch(odt_model* m, const Tensor& roi, const Tensor& hidden, Tensor* out) {
+  const odt_config& cfg = m->cfg;
+  const int FC = cfg.fpn_channels, D = cfg.head_dim, R = cfg.batch * cfg.rpn_topk;
+  ODT_CHECK(FC % 4 == 0 && D % 4 == 0, "use_att_frcnn_head: fpn_channels and head_dim must be multiples of 4");
+  ODT_CHECK(roi.W == R && roi.C == kRoiOut * kRoiOut * FC && hidden.W == R && hidden.c == D,
+            "use_att_frcnn_head: the RoI features or the head's hidden vector are not [B K, ...] rows");
+  struct Var { const char* name; size_t elems; std::string shape; };
+  const Var vars[4] = {{"attention/W", (size_t)9 * FC, "[3,3," + std::to_string(FC) + ",1]"}, {"attention/b", 1, "[1]"},
+                       {"att_trans/W", (size_t)FC * D, "[" + std::to_string(FC) + "," + std::to_string(D) + "]"},
+                       {"att_trans/b", (size_t)D, "[" + std::to_string(D) + "]"}};
+  for (const Var& v : vars) {
+    const std::string name = std::string("fastrcnn/") + v.name;
+    const HostTensor* w = find_w(m, name);
+    ODT_CHECK(w != nullptr, "missing attention box head variable " + name + " (odt_config.use_att_frcnn_head)");
+    ODT_CHECK(w->data.size() == v.elems, "bad shape for " + name + " (" + v.shape + ")");
+    if (name.compare(0, 19, "fastrcnn/attention/") != 0) continue;
+    for (float x : w->data)
+      ODT_CHECK(std::isfinite(x), name + " holds a non-finite value: the reference's softmax over the map's one channel returns NaN "
+                                         "there, not the 1.0 this path rests on (odt_config.use_att_frcnn_head)");
+  }
+  Tensor pooled{}, att{};
+  if (make_tensor(m, "att_pool", 1, 1, R, FC, &pooled)) return 1;
+  {
+    Op op; op.kind = OP_ATT_POOL; op.out = pooled;
+    std::memset(&op.ap, 0, sizeof(op.ap));
+    op.ap.x = roi.d; op.ap.out = pooled.d; op.ap.R = R; op.ap.C = FC;
+    m->ops.push_back(op);
+  }
+  ConvSpec ct("fastrcnn/att_trans", pooled, FC, D);
+  ct.relu = 1; ct.tap = "att_trans";
+  if (conv_layer(m, ct, false, &att)) return 1;
+  m->att_conv = (int)m->convs.size() - 1;
+  ODT_CHECK(att.C == D, "use_att_frcnn_head: the output of fastrcnn/att_trans is not dense");
+  if (make_tensor(m, "att_hidden", 1, 1, R, D, out)) return 1;
+  {
+    Op op; op.kind = OP_ATT_ADD; op.out = *out;
+    std::memset(&op.aa, 0, sizeof(op.aa));
+    op.aa.h = hidden.d; op.aa.a = att.d; op.aa.out = out->d; op.aa.R = R; op.aa.D = D; op.aa.ldh = hidden.C;
+    m->ops.push_back(op);
+  }
+  m->att_head = 1;
+  return 0;
+}
+
 // ---- front end (nn.py:860-896; tf_pad_reverse => pad [3, 2 + pad_to_32]): image pad, conv0, pool0 -> the pooled map
 int front_end(odt_model* m, Tensor* pool) {
   const int B = m->cfg.batch, H = m->cfg.height, W = m->cfg.width;
@@ -600,6 +651,7 @@ int box_head(odt_model* m, const Tensor P[5], const Tensor& props, Tensor* hout)
     if (conv_layer(m, c7, false, &h7)) return 1;
     if (rel) { if (relation_module(m, 1, "fastrcnn/RM_r2", h7, props, geo, "rm_r2", &h7r)) return 1; h7 = h7r; }
   }
+  if (cfg.use_att_frcnn_head) { Tensor ha{}; if (attention_branch(m, roi, h7, &ha)) return 1; h7 = ha; }
   if (concat_cout(m, "fastrcnn/outputs/class", C, "fastrcnn/outputs/box", 4 * C, D, "__headout")) return 1;
   ConvSpec co("fastrcnn/outputs", h7, D, C * 5);
   co.out_ldc = (C * 5 + 3) / 4 * 4; co.tap = "head_out";

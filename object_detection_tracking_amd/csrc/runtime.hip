@@ -163,6 +163,16 @@ static int run_ops(odt_model* m, const void* src, int dtype, hipStream_t st, siz
         if (launch_relation_attention(op.ra, st)) return 1;
         if (m->profile) ODT_HIP(hipEventRecord(m->ev_rel[4 * op.rel + 3], st));
         break;
+      case OP_ATT_POOL:           // --use_att_frcnn_head: the 49-position sum of the RoI features in front of fastrcnn/att_trans
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_att[0], st));
+        if (launch_att_pool(op.ap, st)) return 1;
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_att[1], st));
+        break;
+      case OP_ATT_ADD:            // ... and hidden + relu(att_trans) behind it
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_att[2], st));
+        if (launch_att_add(op.aa, st)) return 1;
+        if (m->profile) ODT_HIP(hipEventRecord(m->ev_att[3], st));
+        break;
       case OP_MASK_SELECT:
         if (launch_mask_select(m->mask_sel, st)) return 1;
         break;
@@ -255,6 +265,12 @@ static int finish_profile(odt_model* m, hipStream_t st) {
     ODT_HIP(hipEventElapsedTime(&t1, m->ev_rel[4 * i + 2], m->ev_rel[4 * i + 3]));
     m->prof_rel_geo_ms[i] += t0; m->prof_rel_attn_ms[i] += t1;
   }
+  if (m->att_head) {
+    float t0 = 0, t1 = 0;
+    ODT_HIP(hipEventElapsedTime(&t0, m->ev_att[0], m->ev_att[1]));
+    ODT_HIP(hipEventElapsedTime(&t1, m->ev_att[2], m->ev_att[3]));
+    m->prof_att_pool_ms += t0; m->prof_att_add_ms += t1;
+  }
   ++m->prof_forwards;
   float tt = 0;
   ODT_HIP(hipEventElapsedTime(&tt, m->ev_total[0], m->ev_total[1]));
@@ -305,6 +321,7 @@ int run_plan(odt_model* m, const void* frames, int dtype, int on_device, hipStre
     while (m->ev_gn.size() < 2 * (size_t)m->gn_ops) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_gn.push_back(e); }
     while (m->ev_gn_roi.size() < 2 * (size_t)m->gn_roi_ops) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_gn_roi.push_back(e); }
     while (m->ev_rel.size() < 4 * (size_t)m->rel_modules) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_rel.push_back(e); }
+    while (m->ev_att.size() < 4 * (size_t)m->att_head) { hipEvent_t e; ODT_HIP(hipEventCreate(&e)); m->ev_att.push_back(e); }
     for (int i = 0; i < 2; ++i) if (!m->ev_total[i]) ODT_HIP(hipEventCreate(&m->ev_total[i]));
     ODT_HIP(hipEventRecord(m->ev_total[0], st));
   }
@@ -396,6 +413,7 @@ int odt_destroy(odt_handle h) {
   for (auto e : h->ev_gn) (void)hipEventDestroy(e);
   for (auto e : h->ev_gn_roi) (void)hipEventDestroy(e);
   for (auto e : h->ev_rel) (void)hipEventDestroy(e);
+  for (auto e : h->ev_att) (void)hipEventDestroy(e);
   for (auto e : h->ev_total) if (e) (void)hipEventDestroy(e);
   for (auto& sl : h->slot) {
     if (sl.pin_in) (void)hipHostFree(sl.pin_in);
@@ -752,6 +770,7 @@ int odt_profile_enable(odt_handle h, int enable) {
   h->prof_gn_ms = 0;
   h->prof_gn_roi_ms = 0;
   for (int i = 0; i < 2; ++i) h->prof_rel_geo_ms[i] = h->prof_rel_attn_ms[i] = 0;
+  h->prof_att_pool_ms = h->prof_att_add_ms = 0;
   h->prof_layer_ms.assign(h->convs.size(), 0.0);
   return 0;
 }
@@ -822,6 +841,14 @@ int odt_describe(odt_handle h, char* buf, int cap) {
   double gn_roi_bytes = 0.0;
   for (const Op& op : h->ops)
     if (op.kind == OP_GN_ROI) gn_roi_bytes += 8.0 * op.gnr.R * op.gnr.hw * op.gnr.C;
+  // ... and of the attention branch: one read of the RoI features and one write of the pooled [R,C]; two reads (hidden, att_trans)
+  // and one write of [R,D]
+  double att_bytes = 0.0;
+  for (const Op& op : h->ops) {
+    if (op.kind == OP_ATT_POOL) att_bytes += 4.0 * op.ap.R * op.ap.C * (49.0 + 1.0);
+    if (op.kind == OP_ATT_ADD) att_bytes += 12.0 * op.aa.R * op.aa.D;
+  }
+  const double att_trans_ms = h->att_conv >= 0 && (size_t)h->att_conv < h->prof_layer_ms.size() ? h->prof_layer_ms[h->att_conv] : 0.0;
   char tmp[8192];
   std::snprintf(tmp, sizeof(tmp),
                 "{\"conv_arith\": \"%s\", \"conv_launches\": %d, \"convs_fused_into_epilogues\": %d, \"exact_f32_mfma_launches\": %d, "
@@ -835,7 +862,8 @@ int odt_describe(odt_handle h, char* buf, int cap) {
                 "\"deform_offset_profiled_ms\": %.6f, \"deform_conv_profiled_ms\": %.6f, \"use_gn\": %d, \"group_norms\": %d, "
                 "\"group_norm_profiled_ms\": %.6f, \"group_norm_floor_bytes\": %.0f, \"box_head\": \"%s\", \"roi_group_norms\": %d, "
                 "\"roi_group_norm_profiled_ms\": %.6f, \"roi_group_norm_floor_bytes\": %.0f, \"relation_modules\": %d, "
-                "\"relation_geo_profiled_ms\": [%.6f, %.6f], \"relation_attention_profiled_ms\": [%.6f, %.6f]}",
+                "\"relation_geo_profiled_ms\": [%.6f, %.6f], \"relation_attention_profiled_ms\": [%.6f, %.6f], "
+                "\"att_frcnn_head\": %d, \"att_head_floor_bytes\": %.0f, \"att_head_profiled_ms\": [%.6f, %.6f, %.6f]}",
                 h->policy.arith != 0 && fam[2] > 0 ? "f32 through fp16x2 / bf16x3 split products"
                     : (h->policy.arith != 0 && fam[1] + fam[3] > 0 ? "f32 through bf16x3 split products" : "exact f32 MFMA"),
                 (int)h->convs.size() - nfused, nfused, fam[0], fam[1] + fam[3], fam[2], h->convs_h2f, h->blocks_fused, h->stem_fused, h->mb_fused, fam[3], fam[1], fam[2], nsk, h->policy.family,
@@ -847,7 +875,8 @@ int odt_describe(odt_handle h, char* buf, int cap) {
                 h->cfg.use_gn != 0 ? 1 : 0, h->gn_ops, h->prof_gn_ms, gn_bytes,
                 h->cfg.graph != ODT_GRAPH_EFFNET && h->cfg.use_conv_frcnn_head != 0 ? "4conv1fc" : (h->rel_modules > 0 ? "2fc+relation" : "2fc"),
                 h->gn_roi_ops, h->prof_gn_roi_ms, gn_roi_bytes, h->rel_modules, h->prof_rel_geo_ms[0], h->prof_rel_geo_ms[1],
-                h->prof_rel_attn_ms[0], h->prof_rel_attn_ms[1]);
+                h->prof_rel_attn_ms[0], h->prof_rel_attn_ms[1],
+                h->att_head, att_bytes, h->prof_att_pool_ms, att_trans_ms, h->prof_att_add_ms);
   ODT_CHECK((int)std::strlen(tmp) < cap, "odt_describe: buffer too small");
   std::strncpy(buf, tmp, cap - 1); buf[cap - 1] = 0;
   return 0;

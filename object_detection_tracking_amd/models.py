@@ -33,7 +33,7 @@ from .nn import get_new_hw
 from .range_guard import RangeGuard
 from .frozen_pb import load_frozen_pb
 from .tf_checkpoint import load_checkpoint
-from .weights import (backbone_block_kind, conv_head_variables, deformable_groups, expand_class_agnostic_box, group_norm_variables, load_npz,
+from .weights import (att_head_variables, backbone_block_kind, conv_head_variables, deformable_groups, expand_class_agnostic_box, group_norm_variables, load_npz,
                       relation_variables, select_partial_classes)
 
 
@@ -139,6 +139,7 @@ class _Engine(object):
     c.use_conv_frcnn_head = int(bool(getattr(config, "use_conv_frcnn_head", False)))      # 4 convs + one FC in place of fc6 / fc7
     c.conv_head_dim = int(getattr(config, "conv_frcnn_head_dim", 256))
     c.add_relation_nn = int(bool(getattr(config, "add_relation_nn", False)))      # RM_r1 / RM_r2 behind fc6 / fc7
+    c.use_att_frcnn_head = int(bool(getattr(config, "use_att_frcnn_head", False)))      # hidden + relu(att_trans(pooled RoI)) in front of the outputs
     B, P, Cn = batch, self.per_im, self.channels
     self._boxes = np.zeros((B, P, 4), np.float32)
     self._probs = np.zeros((B, P), np.float32)
@@ -394,7 +395,7 @@ class _DetectorBase(object):
         raise ValueError("weights: pass a {name: array} dict or set config.model_path to a "
                          "Tensorpack-style .npz (reference obj_detect_tracking.py:417-435), a "
                          "TF checkpoint directory / prefix, or a frozen .pb (--is_load_from_pb)")
-    unsupported = [f for f in ("use_att_frcnn_head", "use_small_object_head", "use_cascade_rcnn")
+    unsupported = [f for f in ("use_small_object_head", "use_cascade_rcnn")
                    if getattr(self.config, f, False)]
     if unsupported:
       raise NotImplementedError("graph variants not built on this path (SURVEY.md 8, out of scope): "
@@ -440,6 +441,28 @@ class _DetectorBase(object):
       if missing:
         raise NotImplementedError("a 4-conv box head (use_conv_frcnn_head) cannot be built from weights without its variables: "
                                   "missing " + ", ".join(missing[:4]) + (" ... (%d in all)" % len(missing) if len(missing) > 4 else ""))
+    if getattr(self.config, "use_att_frcnn_head", False):
+      # --use_att_frcnn_head (models.py:1064-1089, :2682-2707): hidden + relu(att_trans(sum of the RoI's 49 positions)) behind
+      # whichever box head is configured; independent of the backbone, the graph and the mask head.  Checked here, not at the
+      # first frame: a model that cannot run should not construct
+      if getattr(self.config, "use_frcnn_class_agnostic", False):
+        raise NotImplementedError("graph variants not built on this path: use_att_frcnn_head together with use_frcnn_class_agnostic "
+                                  "(set by hand or by version 4 .. 6): the reference's class-agnostic head has no attention branch -- "
+                                  "it takes the flag, ignores it and says nothing")
+      missing = [n for n in att_head_variables(self.config) if n not in weights]
+      if missing:
+        raise NotImplementedError("an attention box head (use_att_frcnn_head) cannot be built from weights without its variables: "
+                                  "missing " + ", ".join(missing))
+      ch, dim = int(self.config.fpn_num_channel), int(self.config.fpn_frcnn_fc_head_dim)
+      for n, shape in zip(att_head_variables(self.config), ((3, 3, ch, 1), (1,), (ch, dim), (dim,))):
+        got = tuple(np.asarray(weights[n]).shape)
+        if int(np.prod(got)) != int(np.prod(shape)):
+          raise ValueError("use_att_frcnn_head: bad shape for %s: %s, the graph has %s" % (n, list(got), list(shape)))
+      for n in ("fastrcnn/attention/W", "fastrcnn/attention/b"):
+        # the map is softmax over ONE channel: exp(l - l) / exp(l - l) = 1 for a finite logit, NaN otherwise
+        if not np.isfinite(np.asarray(weights[n], np.float32)).all():
+          raise ValueError("use_att_frcnn_head: %s holds a non-finite value: the reference's softmax over the attention map's one "
+                           "channel returns NaN there, not the 1.0 this path rests on" % n)
     for f in ("use_resnext", "use_basic_block"):
       # the reference's basic and ResNeXt blocks take use_se and ignore it (nn.py:439-456, 524-549): a graph that silently
       # differs from what a --version 6 checkpoint was trained as is worse than an error
@@ -700,7 +723,8 @@ def config_from_weights(weights, add_mask=False, is_multi=False, **overrides):
   use_dilations=False follows from it: the only published SE model (version 6) is undilated.  A
   ``groupG/block0/conv2_offset/W`` means deformable stage entries (use_deformable, and no dilations); ``conv0/gn/gamma`` means
   GroupNorm in the backbone and the FPN (use_gn); ``fastrcnn/conv0/W`` means the 4-conv + FC box head (use_conv_frcnn_head, its
-  last axis conv_frcnn_head_dim); ``fastrcnn/RM_r1/query_linear/W`` means relation modules in the 2-FC head (add_relation_nn).  No ``group0/block0/conv3/W``
+  last axis conv_frcnn_head_dim); ``fastrcnn/RM_r1/query_linear/W`` means relation modules in the 2-FC head (add_relation_nn);
+  ``fastrcnn/att_trans/W`` behind per-class box outputs means the attention branch (use_att_frcnn_head).  No ``group0/block0/conv3/W``
   means basic blocks (use_basic_block); a ``conv2/W`` of [3,3,C/32,C] means ResNeXt-32x4d (use_resnext)."""
   from .config import make_config
   blocks = [0, 0, 0, 0]
@@ -724,6 +748,8 @@ def config_from_weights(weights, add_mask=False, is_multi=False, **overrides):
     kw.update(use_conv_frcnn_head=True, conv_frcnn_head_dim=int(np.asarray(weights["fastrcnn/conv0/W"]).shape[-1]))
   if "fastrcnn/RM_r1/query_linear/W" in weights:      # relation modules behind fc6 / fc7
     kw.update(add_relation_nn=True)
+  if "fastrcnn/att_trans/W" in weights and not kw["use_frcnn_class_agnostic"]:
+    kw.update(use_att_frcnn_head=True)         # the attention branch (the class-agnostic head has none and never creates the variable)
   if "group0/block0/conv3/W" not in weights:
     kw.update(use_basic_block=True)            # resnet_basicblock: two 3x3 convs, no conv3
   else:

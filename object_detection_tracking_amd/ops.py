@@ -646,6 +646,32 @@ def relation_attention(q, k, v, bias, n, out_init=None, lib=None, device=0):
   return (out.reshape(K, 16, D) if out_init is None else out), float(amax[0])
 
 
+def att_pool(x, lib=None, device=0):
+  """The sum over a RoI's positions as the box head's attention branch runs it under --use_att_frcnn_head (csrc/att_head.hip;
+  reference models.py:1064-1081, whose one-channel softmax map is 1): x [R,49,C] (or [R,7,7,C]), C % 4 == 0.  Returns (out [R,C],
+  recorded |max| of out); out[r, c] is the 49 values added to +0 one after another in row-major order, in float32."""
+  lib = _L(lib)
+  x = f32(x)
+  R, C = x.shape[0], x.shape[-1]
+  assert x.size == R * 49 * C, x.shape
+  out = np.empty((R, C), np.float32); amax = np.zeros(1, np.float32)
+  lib.check(lib.dll.odt_op_att_pool(device, fptr(x), R, C, fptr(out), fptr(amax)))
+  return out, float(amax[0])
+
+
+def att_add(h, a, view=None, lib=None, device=0):
+  """hidden + attended_feat of the same branch (reference models.py:1089): h [R,ldh], of which the first D = view (default ldh)
+  columns are the hidden vector, a [R,D], D % 4 == 0.  Returns (out [R,D], recorded |max| of out)."""
+  lib = _L(lib)
+  h = f32(h); a = f32(a)
+  R, ldh = h.shape
+  D = ldh if view is None else int(view)
+  assert a.shape == (R, D), (a.shape, R, D)
+  out = np.empty((R, D), np.float32); amax = np.zeros(1, np.float32)
+  lib.check(lib.dll.odt_op_att_add(device, fptr(h), ldh, fptr(a), R, D, fptr(out), fptr(amax)))
+  return out, float(amax[0])
+
+
 def se_tail(t2, w3, b3, fc1, fc2, shortcut, lib=None, device=0):
   """The tail of an SE bottleneck (reference nn.py:502-521) as the plan runs it: pool of t2 [B,H,W,ch] -> gate (conv3 + BN
   folded into fc1 = (W [4 ch, ch / 4], b), fc2 = (W [ch / 4, 4 ch], b)) -> conv3 (w3 [ch, 4 ch] with BN folded, + b3) ->

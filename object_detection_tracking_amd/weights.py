@@ -94,6 +94,16 @@ def relation_variables(config):
   return [s + "/" + v for s in RELATION_SCOPES for v in RELATION_VARIABLES]
 
 
+def att_head_variables(config):
+  """Names of the variables a --use_att_frcnn_head graph needs on top of its box head, in the reference's order of creation
+  (fastrcnn_2fc_head, models.py:1064-1089): fastrcnn/attention/{W [3,3,C,1], b [1]} -- the conv behind the one-channel softmax,
+  which the graph owns and whose values cannot reach the output -- and fastrcnn/att_trans/{W [C,dim], b [dim]}.  [] without the
+  flag."""
+  if not getattr(config, "use_att_frcnn_head", False):
+    return []
+  return ["fastrcnn/attention/W", "fastrcnn/attention/b", "fastrcnn/att_trans/W", "fastrcnn/att_trans/b"]
+
+
 def backbone_conv_specs(config):
   """Yield (scope, kh, cin, cout, has_bn, has_bias) for every conv on the path,
   in execution order (reference nn.py:843-1014, models.py:979-1009); cin is W's third dimension -- the channels per
@@ -283,6 +293,16 @@ def synthetic_weights(config, seed=0):
         w[scope + "/" + v] = r_rng.standard_normal((dim, dim), dtype=np.float32) * np.float32(RELATION_SCALES[v] / np.sqrt(dim))
       w[scope + "/output_linear/W"] = r_rng.standard_normal((16 * dim, dim), dtype=np.float32) * np.float32(
           RELATION_SCALES["output_linear/W"] / np.sqrt(16.0 * dim))
+  if getattr(config, "use_att_frcnn_head", False):
+    # --use_att_frcnn_head (models.py:1064-1089) from a generator of its own.  attention/{W,b}: He-init and N(0, 0.02); any
+    # finite values give the same graph.  att_trans reads the SUM of a RoI's 49 positions, which on the synthetic frames is close
+    # to 49 times a single one (the FPN features of a RoI share a mean): He-init divided by 49, so that the branch is of the size
+    # of the hidden vector it is added to (|att_trans| / |fc7| ~ 0.9 on the tests' frames)
+    a_rng = np.random.default_rng([seed, 11])
+    w["fastrcnn/attention/W"] = a_rng.standard_normal((3, 3, ch, 1), dtype=np.float32) * np.float32(np.sqrt(2.0 / (9 * ch)))
+    w["fastrcnn/attention/b"] = a_rng.standard_normal((1,), dtype=np.float32) * np.float32(0.02)
+    w["fastrcnn/att_trans/W"] = a_rng.standard_normal((ch, dim), dtype=np.float32) * np.float32(np.sqrt(2.0 / ch) / 49.0)
+    w["fastrcnn/att_trans/b"] = a_rng.standard_normal((dim,), dtype=np.float32) * np.float32(0.02)
   return w
 
 

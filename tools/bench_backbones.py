@@ -33,6 +33,12 @@ python tools/bench_backbones.py --graph single --batch 1 --backbones r101,r101_r
   shapes: the two attention products (2 K^2 D + 32 K^2 D FLOP) at the exact-f32 MFMA rate, the GEMMs at the rate the fp16x2
   kernels sustain, the bias kernel's K^2 (64 tanh + 1280 FMA) at one v_fma_f32 per lane and clock, a tanh counted as 8 of them
   (an exp and a reciprocal at quarter rate).
+python tools/bench_backbones.py --backbones r101,r101_att [--topk 1000]
+  The attention branch of the box head (--use_att_frcnn_head) next to the plain 2-FC head, two rows that differ in the flag alone,
+  in one run: profiles/att_head_b8_1080p.txt.  A profiled pass times the three launches of the branch: att_pool and att_add
+  (csrc/att_head.hip) each next to its byte floor -- one read of the RoI features and one write of [R,C]; two reads and one write
+  of [R,D]; their sum is describe()'s att_head_floor_bytes -- over the measured copy rate, and fastrcnn/att_trans next to its FLOP
+  at the rate the fp16x2 kernels sustain.  The fp16x2 launch counts of the two rows say whether att_trans runs on those kernels.
 One JSON line per backbone, and one with all of them at the end."""
 import argparse, json, os, subprocess, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -48,7 +54,7 @@ BACKBONES = {"r101": {}, "resnext101": dict(use_resnext=True), "resnet34": dict(
              "r50_gn": dict(resnet50=True, use_gn=True), "r101_gn": dict(use_gn=True),
              "r101_convhead": dict(use_conv_frcnn_head=True), "r50_gn_convhead": dict(resnet50=True, use_gn=True, use_conv_frcnn_head=True),
              "r101_gn_convhead": dict(use_gn=True, use_conv_frcnn_head=True),
-             "r101_relation": dict(add_relation_nn=True)}
+             "r101_relation": dict(add_relation_nn=True), "r101_att": dict(use_att_frcnn_head=True)}
 DEFAULT = ("r101", "resnext101", "resnet34", "resnet18")   # what a run without --backbones measures (profiles/backbones_b8_1080p.txt)
 
 
@@ -184,6 +190,22 @@ def child(a, name):
           "attention_floor_ms": att_fl / F32_MFMA_RATE * 1e3,
           "qk_ms": qk[1] / n, "qk_flop": qk[0], "qk_floor_ms": qk[0] / H2_RATE * 1e3,
           "output_linear_ms": ol[1] / n, "output_linear_flop": ol[0], "output_linear_floor_ms": ol[0] / H2_RATE * 1e3})
+  if d.get("att_frcnn_head", 0):
+    e.profile(True)
+    run(a.steps)
+    dp = e.describe()
+    trans = [(fl, ms) for nm, fl, ms, _ in e.profile_layers() if nm.split("[")[0] == "fastrcnn/att_trans"]
+    e.profile(False)
+    n = max(1, dp["profiled_forwards"])
+    assert len(trans) == 1, trans
+    R, C, D = B * a.topk, int(cfg.fpn_num_channel), int(cfg.fpn_frcnn_fc_head_dim)
+    pool_by, add_by = 4.0 * R * C * (49 + 1), 12.0 * R * D
+    assert pool_by + add_by == dp["att_head_floor_bytes"], (pool_by, add_by, dp["att_head_floor_bytes"])
+    pool_ms, trans_ms, add_ms = (t / n for t in dp["att_head_profiled_ms"])
+    assert abs(trans_ms - trans[0][1] / n) < 1e-9, (trans_ms, trans[0][1] / n)
+    res["att_head"] = {"pool_ms": pool_ms, "pool_bytes": pool_by, "pool_floor_ms": pool_by / COPY_RATE * 1e3,
+                       "add_ms": add_ms, "add_bytes": add_by, "add_floor_ms": add_by / COPY_RATE * 1e3,
+                       "att_trans_ms": trans_ms, "att_trans_flop": trans[0][0], "att_trans_floor_ms": trans[0][0] / H2_RATE * 1e3}
   m.close()
   print(json.dumps(res), flush=True)
   return res
@@ -221,6 +243,8 @@ def main():
     out[name] = res
     line = "%-16s %s %-12s %8.3f ms/step  %7.1f FPS  (%d conv launches, %d fused tails)" % (
         name, res["blocks"], res["block_kind"], res["step_ms"], res["fps"], res["conv_launches"], res["bottleneck_tails_fused"])
+    if any("att_head" in r for r in out.values()) or "r101_att" in names:
+      line += "  [%d on fp16x2]" % res["fp16x2_split_launches"]
     print(line)
     if "group_conv" in res:
       g = res["group_conv"]
@@ -254,6 +278,14 @@ def main():
                 g["module"].split("/")[-1], g["geo_ms"], g["geo_floor_ms"], g["geo_tanh"] / 1e6, g["geo_fma"] / 1e6, g["attention_ms"],
                 g["attention_floor_ms"], g["attention_flop"] / 1e9, F32_MFMA_RATE / 1e12, g["qk_ms"], g["qk_floor_ms"],
                 g["output_linear_ms"], g["output_linear_floor_ms"], g["output_linear_flop"] / 1e9, H2_RATE / 1e12))
+    if "att_head" in res:
+      g = res["att_head"]
+      print("            attention branch (profiled pass): att_pool %.4f ms (floor %.4f: %.1f MB at %.2f TB/s, measured / floor %.2f), "
+            "att_trans %.4f ms (floor %.4f: %.2f GFLOP at %.0f TF, measured / floor %.2f), att_add %.4f ms (floor %.4f: %.1f MB, "
+            "measured / floor %.2f)" % (g["pool_ms"], g["pool_floor_ms"], g["pool_bytes"] / 1e6, COPY_RATE / 1e12, g["pool_ms"] / g["pool_floor_ms"],
+                                        g["att_trans_ms"], g["att_trans_floor_ms"], g["att_trans_flop"] / 1e9, H2_RATE / 1e12,
+                                        g["att_trans_ms"] / g["att_trans_floor_ms"], g["add_ms"], g["add_floor_ms"], g["add_bytes"] / 1e6,
+                                        g["add_ms"] / g["add_floor_ms"]))
   print(json.dumps(out), flush=True)
 
 
